@@ -6,7 +6,18 @@ resident in HBM.  The default workload is BASELINE.json configs[1]: mono 48 kHz,
 throughput mode: one long stream (HOPS hops per step) is processed frame-parallel (chunks of frames with an (R-1)-frame halo, see
 DESIGN.md).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms the box up with untimed steps of the same workload
+(PLAIN_PREHEAT_S seconds, then W steps), times exactly K steps (one timed region), writes the outputs of the last step if --dump-outputs
+is given, and prints the line.  Everything else -- the parity spot check against the CPU oracle, the CPU baseline, the other BASELINE
+configurations, precisions and signal classes, the host-buffer and latency lines, the device-copy ceiling, five timed regions of K steps
+(median reported) and the unabridged record bench_out/bench_detail.json -- runs with --full.
+
+--dump-outputs DIR: what the timed path returned in its last step (the output buffer, float32) as DIR/output.npy, or, when it holds more
+than DUMP_SAMPLES samples, a fixed sample of it (DIR/output_sample.npy + DIR/output_sample_offsets.npy, see dump_outputs).  The input is
+a seeded function of the arguments and the handle's state is reset before the W + K steps, so two builds run with the same arguments can
+be compared output for output.
 
 N > 1: every rank owns an independent stream of the same size on its own GPU (weak scaling, no data-path collective; RCCL only
 carries the barrier and the max-over-ranks reduction of the timing).  Under `torch.distributed.run` the ranks come from the
@@ -16,9 +27,9 @@ only the available devices are measured and the line says so (`requested_gpus`, 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   "roofline":     algorithmic HBM bytes per launch / measured launch duration vs the 8 TB/s peak (HIP events on the launch stream)
   "cpu_baseline": the CPU oracle (a C port of the reference JS, kind "port") timed on ONE host core on a bounded sample of the same
-                  workload, plus the estimate for the reference's own Node.js path (ratio measured by tools/time_reference.js)
+                  workload, plus the estimate for the reference's own Node.js path (ratio measured by tools/time_reference.js) -- --full only
   "configs":      one short measured line per other BASELINE config (C3, a C4 share, C5 with its pitch sweep, the 8-channel form of the
-                  headline shape) and "latency_us": the streaming-quantum histogram of C5 (one launch per quantum; "latency_us_resident": the same on the resident kernel), "latency_us_headline_shape": mono 1024/256 per quantum (launch form / resident kernel) -- N = 1 only, skipped with --no-extras
+                  headline shape) and "latency_us": the streaming-quantum histogram of C5 (one launch per quantum; "latency_us_resident": the same on the resident kernel), "latency_us_headline_shape": mono 1024/256 per quantum (launch form / resident kernel) -- N = 1 and --full only, skipped with --no-extras
 """
 import argparse
 import hashlib
@@ -37,6 +48,30 @@ DTYPE = "f32+f64"           # forward FFT in f32 first, re-run in f64 for the fr
                             # pv_wave_kernel_1024, pv_wave2k_kernel; N >= 4096: f64 forward); shift / inverse FFT / overlap-add in f32, I/O f32
 LINE_BUDGET = 7000          # bytes: the driver keeps the last 8 KB of stdout; the ONE line must fit with room to spare (round-5 verdict, item 5).  What the short ids
                             # ("C3", "C4-share", ...) stand for is spelled out in profiles/bench_workloads.md; the unabridged record of a run goes to bench_detail.json
+PLAIN_PREHEAT_S = 5.0       # a plain one-GPU run: untimed launches of the headline workload before its --warmup steps, so that `value` is the busy box's steady-state rate as
+                            # with --full (a process that starts on an idle box times 1.76 ms/step over 20 steps, 1.715 after 3, 5 or 8 s of preheat or over 2 000 steps)
+DUMP_SAMPLES = 1 << 23      # --dump-outputs: an output up to this many samples is written whole, a larger one as DUMP_SAMPLES samples (32 MiB of float32)
+DUMP_WINDOW = 4096          # ... in windows of this many consecutive samples (16 hops of the headline shape) at seeded offsets
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, y, out_dir):
+    """--dump-outputs: the output buffer of the last timed step (what a caller of pv_process_batch_device receives), float32.
+    Small enough: out_dir/output.npy, shape (channels, samples).  Larger: DUMP_SAMPLES // DUMP_WINDOW windows of DUMP_WINDOW consecutive samples of the
+    row-major (channels, samples) buffer, at window-aligned offsets drawn with DUMP_SEED (the same for every run of the same shape):
+    out_dir/output_sample.npy, shape (windows, DUMP_WINDOW), and out_dir/output_sample_offsets.npy, the flat index of each window's first sample (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = y.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLES:
+        np.save(os.path.join(out_dir, "output.npy"), y.cpu().numpy().astype(np.float32))
+        return
+    nwin = DUMP_SAMPLES // DUMP_WINDOW
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(n // DUMP_WINDOW, size=min(nwin, n // DUMP_WINDOW), replace=False)) * DUMP_WINDOW
+    idx = torch.from_numpy(starts).to(y.device)[:, None] + torch.arange(DUMP_WINDOW, device=y.device)[None, :]
+    np.save(os.path.join(out_dir, "output_sample.npy"), flat[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "output_sample_offsets.npy"), starts.astype(np.float64))
 
 
 def synth_input(torch, nch, nsamples, device, seed):
@@ -148,8 +183,9 @@ def other_input(torch, kind, nch, nsamples, device, seed):
 
 
 def measure(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_t, steps, warmup, label, local_rank, frames_per_chunk=0,
-            pitch_stride=0, ch_per_stream=1, parity_hops=0, seed=0, repeats=1, keep_prefix_hops=0, flags=0, signal="bench", preheat_s=0.0):
-    """One workload: resident input, `warmup` + `steps` launches bracketed by HIP events on the launch stream.  Returns a dict."""
+            pitch_stride=0, ch_per_stream=1, parity_hops=0, seed=0, repeats=1, keep_prefix_hops=0, flags=0, signal="bench", preheat_s=0.0, dump_dir=None):
+    """One workload: resident input, `warmup` + `steps` launches bracketed by HIP events on the launch stream.  Returns a dict.
+    dump_dir: write the output of the last timed launch there (dump_outputs)."""
     import numpy as np
     from phaze_amd import shard
     x = synth_input(torch, nch, T * hop, dev, seed) if signal == "bench" else other_input(torch, signal, nch, T * hop, dev, seed)
@@ -182,8 +218,6 @@ def measure(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_t, steps, warmu
             if s >= 3:
                 break                       # a few streams are enough for a spot check
         parity = float(np.sqrt(err2 / cnt))
-    pv.reset()
-    pv.forward_stats(reset=True)
     regions = []
     with torch.cuda.stream(stream):
         if preheat_s > 0:                         # (see --preheat-seconds: the same workload, untimed, until the box has been busy that long)
@@ -192,6 +226,8 @@ def measure(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_t, steps, warmu
                 for _ in range(16):
                     step()
                 torch.cuda.synchronize()
+        pv.reset()                                # after the preheat, whose launch count depends on the clock: the state of every timed step is fixed by warmup + steps
+        pv.forward_stats(reset=True)
         for _ in range(warmup):
             step()
         for _ in range(max(1, repeats)):          # every region: EXACTLY `steps` launches between barrier + synchronize on both sides
@@ -222,6 +258,8 @@ def measure(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_t, steps, warmu
     alg_bytes = frames * 2 * hop * 4                          # 2*hop*4 B per channel-frame
     achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
     prefix = x[:1, :min(keep_prefix_hops, T) * hop].cpu().numpy() if keep_prefix_hops else None
+    if dump_dir:
+        dump_outputs(torch, y, dump_dir)
     del x, y
     return {"label": label, "frames_per_step_rank": frames, "elapsed": elapsed, "kernel_ms": kernel_ms, "info": info,
             "alg_bytes": alg_bytes, "achieved_gbs": achieved, "parity": parity, "x_prefix": prefix,
@@ -323,7 +361,7 @@ def synth_stream(torch, nch, n0, n1, device):
     return x
 
 
-def measure_time_shard(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_value, steps, warmup, local_rank, rank, world):
+def measure_time_shard(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_value, steps, warmup, local_rank, rank, world, dump_dir=None):
     """ONE stream of T hops split along the time axis over the ranks: rank r owns hops [r T / W, (r + 1) T / W), imports
     {input tail, acc = 0, timeCursor} R - 1 hops before its span (pv_import_state) and recomputes that halo -- no hand-over between ranks.
     Parity: the first hops of every span against the oracle fed the same stream prefix is too slow for spans deep in the stream, so each rank
@@ -389,6 +427,8 @@ def measure_time_shard(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch_valu
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / steps
+    if dump_dir:
+        dump_outputs(torch, y, dump_dir)        # this rank's span (halo included), as the last timed launch left it
     elapsed, kernel_ms = shard.reduce_max([elapsed, kernel_ms], dist, dev)
     ok = shard.reduce_max([0.0 if span_equal in (True, None) else 1.0], dist, dev)[0] == 0.0
     info = pv.info()
@@ -453,16 +493,24 @@ def main():
     ap.add_argument("--pitch", type=float, default=1.5)
     ap.add_argument("--pitch-sweep", action="store_true", help="pitchFactor swept 0.5->2.0 per hop, period 64 hops (BASELINE configs[4]'s schedule) instead of --pitch")
     ap.add_argument("--frames-per-chunk", type=int, default=0)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps launches each; the line reports the median region and lists all (min / median / max)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps launches each; the line reports the median region and lists all (min / median / max).  "
+                                                              "Default: 1 (exactly --steps timed launches), 5 with --full")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend under torch.distributed.run.  nccl (= RCCL) is what the driver runs; gloo exists for ONE test that puts two ranks on one "
                          "GPU (RCCL refuses that) to execute the multi-rank code paths end to end (tests/test_gpu_multirank.py)")
     ap.add_argument("--preheat-seconds", type=float, default=-1.0,
                     help="untimed launches of the headline workload in front of its --warmup steps, until the GPU has been busy this long.  Default: 0 when the other "
-                         "configurations run first (N = 1: they already keep the box busy for ~20 s) and with --no-extras (profiling runs); 8 for N > 1, where the headline is "
-                         "all a rank runs: a freshly leased box spends its first seconds below its sustained clocks, and the per-N values must be measured in the same state")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-config lines and the latency histogram (profiling runs)")
+                         "configurations run first (N = 1 with --full: they already keep the box busy for ~20 s) and with --no-extras (profiling runs); 8 for N > 1, where the headline is "
+                         "all a rank runs: a freshly leased box spends its first seconds below its sustained clocks, and the per-N values must be measured in the same state; "
+                         "PLAIN_PREHEAT_S for a plain N = 1 run, for the same reason")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the parity spot check against the CPU oracle, cpu_baseline, the other configurations (configs, host, "
+                         "latency_us), the device-copy ceiling, five timed regions by default and bench_out/bench_detail.json.  Off by default: a plain run sets up, warms up, "
+                         "times --steps launches, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/*.npy (float32; a fixed, seeded sample of a large output: see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-config lines and the latency histogram; in any run: no default preheat (profiling runs)")
     ap.add_argument("--allow-lib-override", action="store_true", help="accept PHAZE_LIB (A/B builds of the same ABI); recorded in the line")
     ap.add_argument("--pcie", action="store_true", help="also report the host-buffer (PCIe-inclusive) rate")
     ap.add_argument("--time-shard", action="store_true",
@@ -473,6 +521,8 @@ def main():
     ap.add_argument("--scatter-gather", action="store_true",
                     help="N > 1: all streams start on rank 0, are scattered over RCCL, and the results gathered back (reported separately, never in value)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # the library reads no environment; PHAZE_* variables only exist for this harness (PHAZE_LIB = A/B build, explicit opt-in)
     stray = sorted(k for k in os.environ if k.startswith("PHAZE_") and k not in ("PHAZE_LIB", "PHAZE_BENCH_REQUESTED_GPUS", "PHAZE_NO_TORCH_PRELOAD"))
@@ -516,7 +566,8 @@ def main():
         sr, sw = rank, world
         if args.simulate_shard and world == 1:
             sr, sw = (int(v) for v in args.simulate_shard.split("/"))
-        r = measure_time_shard(torch, phaze_amd, dev, dist, fft, hop, nch, T, args.pitch, args.steps, args.warmup, local_rank, sr, sw)
+        r = measure_time_shard(torch, phaze_amd, dev, dist, fft, hop, nch, T, args.pitch, args.steps, args.warmup, local_rank, sr, sw,
+                               dump_dir=args.dump_outputs if rank == 0 else None)
         if args.simulate_shard and world == 1:
             r["elapsed"] *= 1.0        # one span measured; the line below still divides the WHOLE stream by it: only meaningful as a per-span time
         if rank == 0:
@@ -549,7 +600,7 @@ def main():
     # first five or six workloads of a process read 3-5 % slow (the headline 1.78 ms where the same box gives 1.69 once it has been busy for ten seconds), whatever their own
     # warm-up steps -- and `value` is the steady-state rate.  Nothing about the headline's own measurement changes: W untimed steps, then regions of exactly K timed steps.
     xo, xd = {}, {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         # ---- the other configurations, each a short measured entry (same harness, same timing method).  Ids: profiles/bench_workloads.md.
         #      BASELINE's product configurations first, then the unfavourable parameter range, then flavours / signal classes ----
         extras, extras_full = [], []
@@ -594,7 +645,7 @@ def main():
                                ("C4-share-f64", ["--fft", "4096", "--hop", "1024", "--channels", "1024", "--hops", "64", "--pitch", "1.25"]),
                                ("C5-sweep-f64", ["--fft", "8192", "--hop", "2048", "--channels", "8", "--hops", "16384", "--pitch-sweep"]),
                                ("C5-f1.5-f64", ["--fft", "8192", "--hop", "2048", "--channels", "8", "--hops", "16384", "--pitch", "1.5"])):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--allow-lib-override", "--steps", "10", "--warmup", "3",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--allow-lib-override", "--steps", "10", "--warmup", "3",
                                     "--repeats", "3"] + fargs, capture_output=True, text=True, timeout=600, env=dict(os.environ, PHAZE_LIB=flib))
                 try:
                     fj = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -628,10 +679,11 @@ def main():
         xd["latency_us"] = lat
         xo["latency_us"] = {k: {"p50": r4(v["p50"]), "p99": r4(v["p99"]), "budget": r4(v["realtime_budget_us"])} for k, v in lat.items()}
 
-    preheat = args.preheat_seconds if args.preheat_seconds >= 0 else (8.0 if world > 1 else 0.0)
+    preheat = args.preheat_seconds if args.preheat_seconds >= 0 else (8.0 if world > 1 else 0.0 if (xo or args.no_extras) else PLAIN_PREHEAT_S)
     head = measure(torch, phaze_amd, dev, dist, fft, hop, nch, T, pitch, args.steps, args.warmup, "headline", local_rank,
-                   frames_per_chunk=args.frames_per_chunk, parity_hops=96 if rank == 0 else 0, seed=rank, repeats=args.repeats,
-                   keep_prefix_hops=(1 << 19) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else 0, preheat_s=preheat)
+                   frames_per_chunk=args.frames_per_chunk, parity_hops=96 if (rank == 0 and args.full) else 0, seed=rank, repeats=args.repeats,
+                   keep_prefix_hops=(1 << 19) if (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline) else 0, preheat_s=preheat,
+                   dump_dir=args.dump_outputs if rank == 0 else None)
 
     sg_ms = None
     if args.scatter_gather and dist is not None:             # also at world size 1 under torchrun: the collectives still run through RCCL
@@ -674,7 +726,7 @@ def main():
         # the device-copy ceiling of THIS box, measured in this run ("quote the measured copy BW beside" the 8 TB/s peak): a 1 GiB device-to-device
         # copy kernel (torch copy_), read + write bytes over HIP-event time, best of five
         copy_gbs = None
-        if world == 1:
+        if world == 1 and args.full:
             a = torch.empty(1 << 28, dtype=torch.float32, device=dev); b2 = torch.empty_like(a)
             b2.copy_(a); torch.cuda.synchronize()
             best = 1e9
@@ -732,7 +784,7 @@ def main():
         detail["csrc_sha16"] = sha
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(fft, hop, args.pitch_num, head["x_prefix"], "the bench input")
             detail["cpu_baseline"] = cb
             out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": 1, "kind": "port", "sample": cb["sample"][:110], "host_cpus": cb["host_cpus"],
@@ -753,12 +805,13 @@ def main():
         while len(line) > LINE_BUDGET and out.get("configs"):            # (never expected: the entries are sized for ~5 KB) drop flavour entries from the end, say so
             out["configs"].pop(); out["truncated"] = True
             line = json.dumps(out, separators=(",", ":"))
-        try:                                                              # the unabridged record (workload prose, every region, forms of the latency lines) next to the line
-            ddir = os.path.join(ROOT, "gpurun_out")
-            os.makedirs(ddir, exist_ok=True)
-            json.dump(detail, open(os.path.join(ddir, "bench_detail.json"), "w"), indent=1)
-        except Exception:
-            pass
+        if args.full:
+            try:                                                          # the unabridged record (workload prose, every region, forms of the latency lines) next to the line
+                ddir = os.path.join(ROOT, "bench_out")
+                os.makedirs(ddir, exist_ok=True)
+                json.dump(detail, open(os.path.join(ddir, "bench_detail.json"), "w"), indent=1)
+            except Exception:
+                pass
         print(line, flush=True)
     if dist is not None:
         dist.barrier()

@@ -89,7 +89,7 @@ def test_rccl_branch_runs_on_hardware_at_world_size_one():
     barrier, all_reduce(MAX) of the timing on a device tensor, and scatter_streams / gather_streams of the step's input (--scatter-gather).
     A one-GPU box cannot show scaling, but every collective of the N > 1 path executes through RCCL here."""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", "29741",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--hops", "4096", "--no-extras", "--no-cpu-baseline",
+                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--hops", "4096", "--full", "--no-extras", "--no-cpu-baseline",
                         "--scatter-gather"], capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -105,7 +105,7 @@ def test_two_bench_ranks_on_one_gpu_run_the_multi_rank_line_end_to_end():
     statement that the two ranks shared one device (`replicas_measured` 1, no scaling claimed)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HIP_VISIBLE_DEVICES="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29743",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--hops", "8192", "--repeats", "2", "--no-extras", "--no-cpu-baseline",
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--hops", "8192", "--repeats", "2", "--full", "--no-extras", "--no-cpu-baseline",
                         "--dist-backend", "gloo", "--scatter-gather", "--sg-streams", "3"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

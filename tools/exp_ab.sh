@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$1; shift; mkdir -p $OUT
 cd $ROOT
-B="python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extras"
+B="python bench.py --steps 40 --warmup 10 --full --no-cpu-baseline --no-extras"
 run() { n=$1; lib=$2; shift 2
   PHAZE_LIB=$lib $B --allow-lib-override "$@" > $OUT/$n.json 2> $OUT/$n.err
   python - <<PY

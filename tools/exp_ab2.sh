@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$1; shift; mkdir -p $OUT
 cd $ROOT
 names=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do names+=("$1"); shift; done; [ "$1" == "--" ] && shift
-B="python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras --allow-lib-override"
+B="python bench.py --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --no-extras --allow-lib-override"
 one() { n=$1; lib=$2; shift 2
   PHAZE_LIB=$lib $B "$@" > $OUT/$n.json 2> $OUT/$n.err
   python - <<PY

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/${1:-r03a}; mkdir -p $OUT
 cd $ROOT
 export TMPDIR=/tmp
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --allow-lib-override"
+B="python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --allow-lib-override"
 one() { n=$1; lib=$2; shift 2
   PHAZE_LIB=$lib $B "$@" > $OUT/$n.json 2> $OUT/$n.err
   python - <<PY

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/check; mkdir -p $OUT
 cd $ROOT
 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; tail -3 $OUT/pytest.log
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; python -c "
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; python -c "
 import json; j=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 print('HEAD', '%.4g'%j['value'], 'frac %.4f'%j['roofline']['frac'], 'kernel_ms %.4f'%j['roofline']['kernel_ms'], j['dtype'], j['config']['workload'][:70])
 for c in j.get('configs',[]): print('  ', c['workload'][:50], '%.4g'%c['value'], 'frac %.4f'%c['roofline_frac'], 'parity %.2g'%c['parity_rms_vs_oracle'], c['kernel'])

@@ -10,7 +10,7 @@ try:
     print({k:v for k,v in c.items() if 'ower' in k or 'sclk' in k or 'mclk' in k})
 except Exception as e: print('smi?', e)
 "; sleep 0.5; done ) > $OUT.smi 2>&1 &
-PHAZE_LIB=$LIB python bench.py --steps 2500 --warmup 20 --no-cpu-baseline --no-extras --allow-lib-override > $OUT.json 2>$OUT.err
+PHAZE_LIB=$LIB python bench.py --steps 2500 --warmup 20 --full --no-cpu-baseline --no-extras --allow-lib-override > $OUT.json 2>$OUT.err
 wait
 python3 -c "
 import json; j=json.loads(open('$OUT.json').read().strip().splitlines()[-1]); print('kernel_ms', j['roofline']['kernel_ms'])"

@@ -48,8 +48,9 @@ typedef struct pv_handle pv_handle;
  * 3 = round 4: pv_host_alloc / pv_host_free (page-locked host buffers: pv_process_batch pipelines them), PV_FLAG_TEST_NO_HDP_FLUSH,
  *     pv_reset_channels_part + PV_FLAG_HOST_CHANNEL_BOOKKEEPING;
  * 4 = round 5: PV_FLAG_FP64_FORWARD, pv_forward_stats;
- * 5 = round 6: PV_FLAG_TEST_FAIL_SECOND_PIECE (a test hook); no layout or semantic change of anything that existed. */
-#define PV_ABI_VERSION 5
+ * 5 = round 6: PV_FLAG_TEST_FAIL_SECOND_PIECE (a test hook); no layout or semantic change of anything that existed;
+ * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed. */
+#define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
  * ola-processor.js:7-34).  The reference hard-codes fft_size 2048 (phase-vocoder.js:6) and hop 128
@@ -245,6 +246,51 @@ PV_API int pv_synchronize(pv_handle *h);
  * block: hop_size host floats (the newest hop).  Any output pointer may be NULL. */
 PV_API int pv_debug_frame(pv_handle *h, int32_t ch, const float *block, float pitch_factor, double *X,
                           float *mag, int32_t *peak_flags, float *Y);
+
+/* ---- time stretch: tempo change at constant pitch (a separate handle) ----------------------------- */
+/* Phase-locked phase vocoder (Laroche-Dolson identity phase locking) on the pitch path's analysis front end: periodic Hann, fp64 forward
+ * transform, computeMagnitudes / findPeaks (phase-vocoder.js:82-116) and the region-of-influence rule of shiftPeaks at f = 1 (:131-141).
+ * Each frame consumes analysis_hop (ha) input samples and emits synthesis_hop (hs) output samples: the output lasts hs / ha times as long.
+ * Phases are u32 fixed-point turns, so every carried quantity is an integer sum: any split of a stream into calls gives the same bits.
+ * The output lags the input by N - hs samples.  N = 256 .. 8192 (outside: PV_ERR_FFT_SIZE / PV_ERR_UNSUPPORTED as pv_create), ha in 1..N,
+ * hs in 1..N/2 (at least two overlapping output frames; each frame is scaled by hs / N).  See INTEGRATION.md "Time stretch". */
+typedef struct pv_stretch_config {
+    int32_t struct_size;     /* sizeof(pv_stretch_config) as the caller compiled it (PV_STRETCH_CONFIG_INIT sets it)          */
+    int32_t fft_size;        /* N, power of two, 256 .. 8192                                                                      */
+    int32_t analysis_hop;    /* ha: input samples per frame, 1 .. N                                                              */
+    int32_t synthesis_hop;   /* hs: output samples per frame, 1 .. N/2                                                           */
+    int32_t max_channels;    /* channel slots (0 => 1)                                                                           */
+    int32_t max_frames;      /* host-pointer calls: staging size in frames (0 => 1); longer calls are staged in pieces          */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_stretch_config;
+#define PV_STRETCH_CONFIG_INIT { (int32_t)sizeof(pv_stretch_config), 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_stretch pv_stretch;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_stretch_last_error(NULL). */
+PV_API int pv_stretch_create(const pv_stretch_config *cfg, pv_stretch **out);
+PV_API int pv_stretch_destroy(pv_stretch *h);
+/* Zero the state of every channel slot (a freshly created handle). */
+PV_API int pv_stretch_reset(pv_stretch *h);
+/* Text of the last failure on this handle (h == NULL: of the last failed pv_stretch_create on this thread). */
+PV_API const char *pv_stretch_last_error(const pv_stretch *h);
+/* nframes frames for channel slots 0 .. nch-1: in[c*in_stride .. + nframes*ha) -> out[c*out_stride .. + nframes*hs).
+ * Host pointers, synchronous. */
+PV_API int pv_stretch_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes,
+                              int64_t in_stride, int64_t out_stride);
+/* The same on DEVICE pointers, asynchronous on the handle's stream (pv_stretch_set_stream / pv_stretch_synchronize). */
+PV_API int pv_stretch_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch,
+                                     int32_t nframes, int64_t in_stride, int64_t out_stride);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_stretch_set_stream(pv_stretch *h, void *hip_stream);
+PV_API int pv_stretch_synchronize(pv_stretch *h);
+/* State of ONE channel slot: hist[N - ha] newest input samples, acc[N - hs] pending overlap-add sums, phi[N/2 + 1] previous analysis phase,
+ * psi[N/2 + 1] synthesis phase (u32 turns).  A handle that imports what another exported continues bit for bit.  Synchronous; any pointer may be
+ * NULL (skipped). */
+PV_API int pv_stretch_export_state(pv_stretch *h, int32_t ch, float *hist, float *acc, uint32_t *phi, uint32_t *psi);
+PV_API int pv_stretch_import_state(pv_stretch *h, int32_t ch, const float *hist, const float *acc,
+                                   const uint32_t *phi, const uint32_t *psi);
 
 #ifdef __cplusplus
 }

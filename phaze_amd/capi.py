@@ -23,6 +23,8 @@ EXPORTS = [
     "pv_set_stream", "pv_synchronize", "pv_debug_frame", "pv_export_state", "pv_import_state", "pv_abi_version",
     "pv_process_begin", "pv_process_end", "pv_device_count", "pv_host_alloc", "pv_host_free", "pv_reset_channels_part",
     "pv_forward_stats",
+    "pv_stretch_create", "pv_stretch_destroy", "pv_stretch_reset", "pv_stretch_last_error", "pv_stretch_process", "pv_stretch_process_device",
+    "pv_stretch_set_stream", "pv_stretch_synchronize", "pv_stretch_export_state", "pv_stretch_import_state",
 ]
 
 
@@ -36,12 +38,21 @@ class _Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "fft_size", "hop_size", "max_channels", "max_hops", "device_id", "frames_per_chunk", "flags")]
 
 
+class _StretchConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "fft_size", "analysis_hop", "synthesis_hop", "max_channels", "max_frames", "device_id", "flags")]
+
+
+def make_stretch_config(fft_size, analysis_hop, synthesis_hop, max_channels=1, max_frames=1, device_id=0, flags=0):
+    """pv_stretch_config with struct_size filled in (the C side's PV_STRETCH_CONFIG_INIT)."""
+    return _StretchConfig(C.sizeof(_StretchConfig), fft_size, analysis_hop, synthesis_hop, max_channels, max_frames, device_id, flags)
+
+
 def make_config(fft_size, hop_size, max_channels=1, max_hops=1, device_id=0, frames_per_chunk=0, flags=0):
     """pv_config with struct_size filled in (the C side's PV_CONFIG_INIT)."""
     return _Config(C.sizeof(_Config), fft_size, hop_size, max_channels, max_hops, device_id, frames_per_chunk, flags)
 
 
-ABI_VERSION = 5          # PV_ABI_VERSION of include/phaze_amd.h this binding was written against (checked at load time)
+ABI_VERSION = 6          # PV_ABI_VERSION of include/phaze_amd.h this binding was written against (checked at load time)
 
 
 # pv_config.flags (include/phaze_amd.h): explicit A/B switches; the library reads no environment variables
@@ -111,8 +122,20 @@ def load_library():
     L.pv_debug_frame.argtypes = [vp, C.c_int32, fp, C.c_float, C.POINTER(C.c_double), fp, C.POINTER(C.c_int32), fp]
     L.pv_export_state.argtypes = [vp, C.c_int32, fp, fp, C.POINTER(C.c_int64)]
     L.pv_import_state.argtypes = [vp, C.c_int32, fp, fp, C.c_int64]
+    up = C.POINTER(C.c_uint32)
+    L.pv_stretch_create.argtypes = [C.POINTER(_StretchConfig), C.POINTER(vp)]
+    L.pv_stretch_destroy.argtypes = [vp]
+    L.pv_stretch_reset.argtypes = [vp]
+    L.pv_stretch_last_error.argtypes = [vp]
+    L.pv_stretch_last_error.restype = C.c_char_p
+    L.pv_stretch_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+    L.pv_stretch_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+    L.pv_stretch_set_stream.argtypes = [vp, vp]
+    L.pv_stretch_synchronize.argtypes = [vp]
+    L.pv_stretch_export_state.argtypes = [vp, C.c_int32, fp, fp, up, up]
+    L.pv_stretch_import_state.argtypes = [vp, C.c_int32, fp, fp, up, up]
     for n in EXPORTS:
-        if n not in ("pv_last_error", "pv_status_string"):
+        if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
@@ -384,3 +407,91 @@ class PhaseVocoder:
         self._check(self._L.pv_debug_frame(self._h, ch, _fp(block), C.c_float(float(pitch)), X.ctypes.data_as(C.POINTER(C.c_double)),
                                            _fp(mag), flags.ctypes.data_as(C.POINTER(C.c_int32)), _fp(Y)))
         return {"X": X, "mag": mag, "flags": flags, "Y": Y}
+
+
+class TimeStretch:
+    """Phase-locked time stretch (pv_stretch_*): tempo change at constant pitch.  Each frame consumes `analysis_hop` input samples and emits
+    `synthesis_hop` output samples, so the output lasts synthesis_hop / analysis_hop times as long; it lags the input by fft_size - synthesis_hop
+    samples.  State carries across calls: any split of a stream into calls gives the same bits."""
+
+    def __init__(self, fft_size, analysis_hop, synthesis_hop, max_channels=1, max_frames=1, device_id=0):
+        self._L = load_library()
+        self._h = C.c_void_p()
+        cfg = make_stretch_config(fft_size, analysis_hop, synthesis_hop, max_channels, max_frames, device_id, 0)
+        rc = self._L.pv_stretch_create(C.byref(cfg), C.byref(self._h))
+        if rc != PV_OK:
+            msg = self._L.pv_stretch_last_error(None).decode()
+            self._h = C.c_void_p()
+            if rc == PV_ERR_FFT_SIZE:
+                raise ValueError(msg)
+            raise PvError(rc, msg)
+        self.fft_size, self.analysis_hop, self.synthesis_hop = fft_size, analysis_hop, synthesis_hop
+        self.max_channels, self.max_frames = max_channels, max_frames
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.pv_stretch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != PV_OK:
+            raise PvError(rc, self._L.pv_stretch_last_error(self._h).decode())
+
+    def reset(self):
+        self._check(self._L.pv_stretch_reset(self._h))
+
+    def process(self, x):
+        """x: float32[nch, nframes * analysis_hop] (host) -> float32[nch, nframes * synthesis_hop] for channel slots 0 .. nch-1."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        nframes = n // self.analysis_hop
+        if nframes * self.analysis_hop != n:
+            raise ValueError("the input length must be a whole number of analysis hops")
+        y = np.empty((nch, nframes * self.synthesis_hop), np.float32)
+        if nch and nframes:
+            self._check(self._L.pv_stretch_process(self._h, _fp(x), _fp(y), nch, nframes, n, nframes * self.synthesis_hop))
+        return y
+
+    def process_device(self, d_in, d_out, nch, nframes, in_stride, out_stride):
+        """Raw device pointers (ints).  Asynchronous on the handle's stream."""
+        self._check(self._L.pv_stretch_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, in_stride, out_stride))
+
+    def set_stream(self, hip_stream):
+        self._check(self._L.pv_stretch_set_stream(self._h, C.c_void_p(hip_stream)))
+
+    def synchronize(self):
+        self._check(self._L.pv_stretch_synchronize(self._h))
+
+    def export_state(self, ch):
+        """(hist[N - ha], acc[N - hs], phi[N/2 + 1] u32, psi[N/2 + 1] u32) of channel slot `ch`."""
+        N, H = self.fft_size, self.fft_size // 2 + 1
+        hist = np.zeros(max(N - self.analysis_hop, 1), np.float32)
+        acc = np.zeros(N - self.synthesis_hop, np.float32)
+        phi, psi = np.zeros(H, np.uint32), np.zeros(H, np.uint32)
+        up = C.POINTER(C.c_uint32)
+        self._check(self._L.pv_stretch_export_state(self._h, ch, _fp(hist), _fp(acc), phi.ctypes.data_as(up), psi.ctypes.data_as(up)))
+        return hist[:N - self.analysis_hop], acc, phi, psi
+
+    def import_state(self, ch, hist=None, acc=None, phi=None, psi=None):
+        N, H = self.fft_size, self.fft_size // 2 + 1
+        up = C.POINTER(C.c_uint32)
+
+        def chk(a, n, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != n:
+                raise ValueError(f"state array of {a.size} values, {n} expected")
+            return a
+        hist, acc = chk(hist, N - self.analysis_hop, np.float32), chk(acc, N - self.synthesis_hop, np.float32)
+        phi, psi = chk(phi, H, np.uint32), chk(psi, H, np.uint32)
+        self._check(self._L.pv_stretch_import_state(self._h, ch, _fp(hist) if hist is not None and hist.size else None, _fp(acc) if acc is not None else None,
+                                                    phi.ctypes.data_as(up) if phi is not None else None, psi.ctypes.data_as(up) if psi is not None else None))

@@ -1,0 +1,32 @@
+// pv_stretch.h -- launch interface of the time-stretch kernels (internal; the public ABI is include/phaze_amd.h, pv_stretch_*).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+// Per-channel state slot, in floats / u32 words: hist[N - ha] | acc[N - hs] | phi[H] | psi[H]  (H = N/2 + 1).
+inline long pv_stretch_state_stride(int N, int ha, int hs) { return (long)(N - ha) + (N - hs) + 2L * (N / 2 + 1); }
+
+struct PvStretchParams {
+    const float *in;          // channel c at in + c * in_stride: nframes * ha samples
+    float *out;               // channel c at out + c * out_stride: nframes * hs samples
+    long in_stride, out_stride;
+    int nframes, nch;
+    int ha, hs;
+    int F;                    // frames per chain (>= halo + 1 whenever there is more than one chain)
+    int nchains;              // chains per channel
+    int halo;                 // (N - 1) / hs: earlier frames that overlap a frame's first output sample
+    float ola_scale;          // hs / N = 1 / R_s
+    const float *state_in;    // [nch][state_stride] carried state in
+    float *state_out;         // [nch][state_stride] carried state out (the host copies it back behind the launch)
+    long state_stride;
+    unsigned *sums;           // [nch][nchains][2][H]: pass A writes {main, halo} advance sums, the scan turns the halo slot into pass B's start carry
+    const double2 *tw64;      // exp(-2 pi j k / N), k in [0, N)
+    const float2 *tw32;
+    const float *hann;        // periodic Hann, f32, N values
+};
+
+bool pv_stretch_supported(int log2n);                     // N = 256 .. 8192
+size_t pv_stretch_lds_bytes(int log2n, bool pass_b);
+int pv_stretch_threads();
+// pass A + scan + pass B on `st`; the caller then copies state_out back into its state
+hipError_t pv_launch_stretch(int log2n, const PvStretchParams &p, hipStream_t st);

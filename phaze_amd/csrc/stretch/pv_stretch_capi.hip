@@ -1,0 +1,299 @@
+// pv_stretch_capi.hip -- host side of the pv_stretch_* entry points of include/phaze_amd.h (phase-locked time stretch).
+//
+// Owns one time-stretch handle's device state -- per channel slot hist[N - ha] | acc[N - hs] | phi[H] | psi[H] (pv_stretch.h) -- and turns calls
+// into pass A + scan + pass B launches (pv_stretch_kernels.hip).  No CPU compute path: without a HIP device pv_stretch_create fails with PV_ERR_DEVICE.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../../include/phaze_amd.h"
+#include "pv_stretch.h"
+
+namespace {
+constexpr uint32_t kStretchMagic = 0x50565453u;   // 'PVTS'
+thread_local char g_stretch_create_err[256] = "";
+}  // namespace
+
+struct pv_stretch {
+    uint32_t magic;
+    int N, log2n, ha, hs, H, halo;
+    int max_channels, max_frames, device, cus;
+    hipStream_t own_stream, stream;
+    double2 *d_tw64;
+    float2 *d_tw32;
+    float *d_hann;
+    long stride;                 // floats per channel slot of the state
+    float *d_state, *d_state_out;
+    unsigned *d_sums;            // pass A / scan / pass B exchange, grown on demand
+    size_t sums_cap;             // (in u32 words)
+    float *d_stage_in, *d_stage_out;   // host-pointer calls: max_channels x max_frames frames
+    char err[256];
+};
+
+namespace {
+
+int sfail(pv_stretch *h, int code, const char *msg)
+{
+    if (h) snprintf(h->err, sizeof h->err, "%s", msg);
+    else snprintf(g_stretch_create_err, sizeof g_stretch_create_err, "%s", msg);
+    return code;
+}
+
+int sfail_hip(pv_stretch *h, hipError_t e, const char *what)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    return sfail(h, PV_ERR_DEVICE, buf);
+}
+
+#define SCHK(h, call)                                              \
+    do {                                                           \
+        hipError_t e_ = (call);                                    \
+        if (e_ != hipSuccess) return sfail_hip((h), e_, #call);    \
+    } while (0)
+
+bool slive(const pv_stretch *h) { return h && h->magic == kStretchMagic; }
+
+// Frames per chain: one round of the workgroups the chip holds at once, but never fewer than four times the (halo + 1) frames a chain recomputes.
+int pick_chain(const pv_stretch *h, int nch, int nframes)
+{
+    const size_t lds = pv_stretch_lds_bytes(h->log2n, true);
+    long per_cu = (long)((160 * 1024) / (lds + 512));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const long slots = per_cu * h->cus;
+    long chains = slots / (nch > 0 ? nch : 1);
+    if (chains < 1) chains = 1;
+    long F = (nframes + chains - 1) / chains;
+    if (F < 4L * (h->halo + 1)) F = 4L * (h->halo + 1);
+    if (F > nframes) F = nframes;
+    return (int)F;
+}
+
+// One launch over channel slots [0, nch): device pointers, asynchronous on h->stream.
+int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, long in_stride, long out_stride)
+{
+    PvStretchParams p;
+    memset(&p, 0, sizeof p);
+    p.in = d_in; p.out = d_out; p.in_stride = in_stride; p.out_stride = out_stride;
+    p.nframes = nframes; p.nch = nch; p.ha = h->ha; p.hs = h->hs;
+    p.F = pick_chain(h, nch, nframes);
+    p.nchains = (nframes + p.F - 1) / p.F;
+    p.halo = h->halo;
+    p.ola_scale = (float)((double)h->hs / (double)h->N);
+    p.state_in = h->d_state; p.state_out = h->d_state_out; p.state_stride = h->stride;
+    p.tw64 = h->d_tw64; p.tw32 = h->d_tw32; p.hann = h->d_hann;
+    const size_t words = (size_t)nch * (size_t)p.nchains * 2 * (size_t)h->H;
+    if (words > h->sums_cap) {
+        SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still use the old buffer
+        if (h->d_sums) (void)hipFree(h->d_sums);
+        h->d_sums = nullptr; h->sums_cap = 0;
+        SCHK(h, hipMalloc(&h->d_sums, words * sizeof(unsigned)));
+        h->sums_cap = words;
+    }
+    p.sums = h->d_sums;
+    SCHK(h, pv_launch_stretch(h->log2n, p, h->stream));
+    SCHK(h, hipMemcpyAsync(h->d_state, h->d_state_out, sizeof(float) * (size_t)nch * (size_t)h->stride, hipMemcpyDeviceToDevice, h->stream));
+    return PV_OK;
+}
+
+int check_call(pv_stretch *h, const void *in, const void *out, int32_t nch, int32_t nframes, int64_t in_stride, int64_t out_stride)
+{
+    if (!in || !out) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: null buffer");
+    if (nch < 0 || nframes < 0) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: negative channel or frame count");
+    if (nch > h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_process: more channels than max_channels");
+    if (nch > 1 && (in_stride < (int64_t)nframes * h->ha || out_stride < (int64_t)nframes * h->hs))
+        return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: channel strides shorter than nframes * hop");
+    return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *pv_stretch_last_error(const pv_stretch *h) { return slive(h) ? h->err : g_stretch_create_err; }
+
+int pv_stretch_create(const pv_stretch_config *cfg, pv_stretch **out)
+{
+    if (!cfg || !out) return sfail(nullptr, PV_ERR_ARGUMENT, "pv_stretch_create: null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(pv_stretch_config))
+        return sfail(nullptr, PV_ERR_ARGUMENT, "pv_stretch_create: pv_stretch_config.struct_size does not match this library (start from PV_STRETCH_CONFIG_INIT)");
+    if (cfg->flags != 0) return sfail(nullptr, PV_ERR_ARGUMENT, "pv_stretch_create: unknown bits in pv_stretch_config.flags (must be 0)");
+    const int N = cfg->fft_size, ha = cfg->analysis_hop, hs = cfg->synthesis_hop;
+    if (N <= 1 || (N & (N - 1)) != 0) return sfail(nullptr, PV_ERR_FFT_SIZE, "FFT size must be a power of two and bigger than 1");
+    int log2n = 0;
+    while ((1 << log2n) < N) log2n++;
+    if (!pv_stretch_supported(log2n)) return sfail(nullptr, PV_ERR_UNSUPPORTED, "fft_size must be within 256..8192 for the time-stretch kernels");
+    if (ha < 1 || ha > N) return sfail(nullptr, PV_ERR_ARGUMENT, "analysis_hop must be within 1..fft_size");
+    if (hs < 1 || hs > N / 2) return sfail(nullptr, PV_ERR_ARGUMENT, "synthesis_hop must be within 1..fft_size/2 (at least two overlapping frames, R_s = N / hs >= 2)");
+    const int maxch = cfg->max_channels > 0 ? cfg->max_channels : 1;
+    const int maxfr = cfg->max_frames > 0 ? cfg->max_frames : 1;
+    if (maxch > 65535) return sfail(nullptr, PV_ERR_UNSUPPORTED, "max_channels above 65535 (grid.y limit)");
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return sfail(nullptr, PV_ERR_DEVICE, "no HIP device available (this library has no CPU path)"); }
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return sfail(nullptr, PV_ERR_ARGUMENT, "device_id out of range");
+
+    pv_stretch *h = (pv_stretch *)calloc(1, sizeof(pv_stretch));
+    if (!h) return sfail(nullptr, PV_ERR_DEVICE, "pv_stretch_create: out of host memory");
+    h->magic = kStretchMagic;
+    h->N = N; h->log2n = log2n; h->ha = ha; h->hs = hs; h->H = N / 2 + 1; h->halo = (N - 1) / hs;
+    h->max_channels = maxch; h->max_frames = maxfr; h->device = cfg->device_id;
+    h->stride = pv_stretch_state_stride(N, ha, hs);
+
+#define CCHK(call)                                                         \
+    do {                                                                   \
+        hipError_t e2_ = (call);                                           \
+        if (e2_ != hipSuccess) {                                           \
+            int rc_ = sfail_hip(nullptr, e2_, #call);                      \
+            pv_stretch_destroy(h);                                         \
+            return rc_;                                                    \
+        }                                                                  \
+    } while (0)
+    CCHK(hipSetDevice(h->device));
+    hipDeviceProp_t prop;
+    CCHK(hipGetDeviceProperties(&prop, h->device));
+    h->cus = prop.multiProcessorCount;
+    CCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    h->stream = h->own_stream;
+    // twiddles exp(-2 pi j k / N) and the periodic Hann window: the pitch path's tables (pv_capi.hip)
+    std::vector<double2> tw64(N);
+    std::vector<float2> tw32(N);
+    std::vector<float> hann(N);
+    for (int k = 0; k < N; k++) {
+        const double ang = 2.0 * M_PI * (double)k / (double)N;
+        tw64[k] = double2{cos(ang), -sin(ang)};
+        hann[k] = (float)(0.5 * (1.0 - cos(ang)));
+    }
+    tw64[0] = double2{1, 0};
+    tw64[N / 4] = double2{0, -1};
+    tw64[N / 2] = double2{-1, 0};
+    tw64[3 * N / 4] = double2{0, 1};
+    for (int k = 0; k < N; k++) tw32[k] = float2{(float)tw64[k].x, (float)tw64[k].y};
+    CCHK(hipMalloc(&h->d_tw64, sizeof(double2) * N));
+    CCHK(hipMalloc(&h->d_tw32, sizeof(float2) * N));
+    CCHK(hipMalloc(&h->d_hann, sizeof(float) * N));
+    CCHK(hipMemcpy(h->d_tw64, tw64.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
+    CCHK(hipMemcpy(h->d_tw32, tw32.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+    CCHK(hipMemcpy(h->d_hann, hann.data(), sizeof(float) * N, hipMemcpyHostToDevice));
+    const size_t state = sizeof(float) * (size_t)maxch * (size_t)h->stride;
+    CCHK(hipMalloc(&h->d_state, state));
+    CCHK(hipMalloc(&h->d_state_out, state));
+    CCHK(hipMemset(h->d_state, 0, state));
+    CCHK(hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)maxch * (size_t)maxfr * ha));
+    CCHK(hipMalloc(&h->d_stage_out, sizeof(float) * (size_t)maxch * (size_t)maxfr * hs));
+#undef CCHK
+    *out = h;
+    return PV_OK;
+}
+
+int pv_stretch_destroy(pv_stretch *h)
+{
+    if (!h) return PV_ERR_ARGUMENT;
+    if (!slive(h)) return PV_ERR_DESTROYED;
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    void *ptrs[] = {h->d_tw64, h->d_tw32, h->d_hann, h->d_state, h->d_state_out, h->d_sums, h->d_stage_in, h->d_stage_out};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    (void)hipGetLastError();
+    h->magic = 0;
+    free(h);
+    return PV_OK;
+}
+
+int pv_stretch_reset(pv_stretch *h)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipMemsetAsync(h->d_state, 0, sizeof(float) * (size_t)h->max_channels * (size_t)h->stride, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return PV_OK;
+}
+
+int pv_stretch_set_stream(pv_stretch *h, void *hip_stream)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    SCHK(h, hipStreamSynchronize(h->stream));                          // work queued on the old stream is ordered before the new one's
+    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
+    return PV_OK;
+}
+
+int pv_stretch_synchronize(pv_stretch *h)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return PV_OK;
+}
+
+int pv_stretch_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    const int rc = check_call(h, d_in, d_out, nch, nframes, in_stride, out_stride);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    return run(h, d_in, d_out, nch, nframes, (long)in_stride, (long)out_stride);
+}
+
+int pv_stretch_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    const int rc = check_call(h, in, out, nch, nframes, in_stride, out_stride);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    // pieces of at most max_frames frames through the staging buffers: the state carries across pieces exactly as across calls
+    const long sin = (long)h->max_frames * h->ha, sout = (long)h->max_frames * h->hs;
+    const size_t ipitch = sizeof(float) * (size_t)(nch > 1 ? in_stride : (int64_t)nframes * h->ha);
+    const size_t opitch = sizeof(float) * (size_t)(nch > 1 ? out_stride : (int64_t)nframes * h->hs);
+    for (int f0 = 0; f0 < nframes; f0 += h->max_frames) {
+        const int nf = nframes - f0 < h->max_frames ? nframes - f0 : h->max_frames;
+        SCHK(h, hipMemcpy2DAsync(h->d_stage_in, sizeof(float) * sin, in + (long)f0 * h->ha, ipitch,
+                                 sizeof(float) * (size_t)nf * h->ha, nch, hipMemcpyHostToDevice, h->stream));
+        const int r = run(h, h->d_stage_in, h->d_stage_out, nch, nf, sin, sout);
+        if (r != PV_OK) return r;
+        SCHK(h, hipMemcpy2DAsync(out + (long)f0 * h->hs, opitch, h->d_stage_out, sizeof(float) * sout,
+                                 sizeof(float) * (size_t)nf * h->hs, nch, hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PV_OK;
+}
+
+int pv_stretch_export_state(pv_stretch *h, int32_t ch, float *hist, float *acc, uint32_t *phi, uint32_t *psi)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    if (ch < 0 || ch >= h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_export_state: channel slot out of range");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    const float *s = h->d_state + (size_t)ch * h->stride;
+    const size_t nh = (size_t)(h->N - h->ha), na = (size_t)(h->N - h->hs), H = (size_t)h->H;
+    if (hist && nh) SCHK(h, hipMemcpy(hist, s, sizeof(float) * nh, hipMemcpyDeviceToHost));
+    if (acc && na) SCHK(h, hipMemcpy(acc, s + nh, sizeof(float) * na, hipMemcpyDeviceToHost));
+    if (phi) SCHK(h, hipMemcpy(phi, s + nh + na, sizeof(uint32_t) * H, hipMemcpyDeviceToHost));
+    if (psi) SCHK(h, hipMemcpy(psi, s + nh + na + H, sizeof(uint32_t) * H, hipMemcpyDeviceToHost));
+    return PV_OK;
+}
+
+int pv_stretch_import_state(pv_stretch *h, int32_t ch, const float *hist, const float *acc, const uint32_t *phi, const uint32_t *psi)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    if (ch < 0 || ch >= h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_import_state: channel slot out of range");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    float *s = h->d_state + (size_t)ch * h->stride;
+    const size_t nh = (size_t)(h->N - h->ha), na = (size_t)(h->N - h->hs), H = (size_t)h->H;
+    if (hist && nh) SCHK(h, hipMemcpy(s, hist, sizeof(float) * nh, hipMemcpyHostToDevice));
+    if (acc && na) SCHK(h, hipMemcpy(s + nh, acc, sizeof(float) * na, hipMemcpyHostToDevice));
+    if (phi) SCHK(h, hipMemcpy(s + nh + na, phi, sizeof(uint32_t) * H, hipMemcpyHostToDevice));
+    if (psi) SCHK(h, hipMemcpy(s + nh + na + H, psi, sizeof(uint32_t) * H, hipMemcpyHostToDevice));
+    return PV_OK;
+}
+
+}  // extern "C"

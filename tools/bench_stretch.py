@@ -1,0 +1,85 @@
+"""Throughput of the time-stretch kernels (pv_stretch_process_device), one JSON line per shape.
+
+Same discipline as bench.py: HBM-resident input, `--warmup` untimed launches, then `--steps` launches bracketed by HIP events on the launch stream.
+frames/s counts channel-frames; `hbm_fraction` is the algorithmic traffic of a frame, (ha + hs) * 4 B, against 8 TB/s.  Two comparison lines time the
+pitch kernel on the same input: the headline form (pitchFactor 1.5), and the GPU part of the host speed path (pitch-shift-cli.js --speed 1.25: the input
+resampled to 0.8x on the host, then the pitch kernel at pitchFactor 1 / 1.25), which produces the same output duration as a 1.25x stretch.
+
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 8e12
+
+
+def _time(torch, stream, fn, steps, warmup):
+    with torch.cuda.stream(stream):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(steps):
+            fn()
+        e1.record(stream)
+        torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def stretch_line(torch, phaze_amd, N, ha, hs, nch, T, steps, warmup):
+    x = (torch.rand((nch, T * ha), device="cuda") - 0.5).contiguous()
+    y = torch.empty((nch, T * hs), device="cuda")
+    ts = phaze_amd.TimeStretch(N, ha, hs, max_channels=nch)
+    stream = torch.cuda.Stream()
+    ts.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ts.process_device(x.data_ptr(), y.data_ptr(), nch, T, T * ha, T * hs), steps, warmup)
+    ts.close()
+    frames = nch * T
+    return {"kernel": "pv_stretch", "fft": N, "analysis_hop": ha, "synthesis_hop": hs, "channels": nch, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
+            "frames_per_s": frames / (ms * 1e-3), "hbm_fraction": frames * (ha + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
+def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
+    x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
+    y = torch.empty_like(x)
+    p = torch.full((T,), pitch, dtype=torch.float32, device="cuda")
+    pv = phaze_amd.PhaseVocoder(fft_size=N, hop_size=hop, max_channels=nch, max_hops=1)
+    stream = torch.cuda.Stream()
+    pv.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: pv.process_batch_device(x.data_ptr(), y.data_ptr(), nch, T, T * hop, p.data_ptr(), 0, 1), steps, warmup)
+    kernel = pv.info()["kernel_name"]
+    pv.close()
+    frames = nch * T
+    return {"kernel": kernel, "label": label, "fft": N, "hop": hop, "pitch": pitch, "channels": nch, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
+            "frames_per_s": frames / (ms * 1e-3), "hbm_fraction": frames * 2 * hop * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=1 << 20, help="frames per channel of the mono 1024 shape (the others keep its sample count)")
+    ap.add_argument("--no-compare", action="store_true", help="skip the two pitch-kernel comparison lines")
+    args = ap.parse_args()
+    import torch
+    import phaze_amd
+    T = args.frames
+    shapes = [(1024, 256, 320, 1, T), (2048, 512, 640, 2, T // 2), (4096, 1024, 1280, 8, T // 8)]
+    for N, ha, hs, nch, t in shapes:
+        print(json.dumps(stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup)), flush=True)
+    if not args.no_compare:
+        print(json.dumps(pitch_line(torch, phaze_amd, "pitch headline, same input", 1024, 256, 1, T, 1.5, args.steps, args.warmup)), flush=True)
+        # --speed 1.25: 0.8x as many input frames after the host resampler, pitch 1 / 1.25: the same output duration as the 1.25x stretch above
+        print(json.dumps(pitch_line(torch, phaze_amd, "speed path GPU part (--speed 1.25)", 1024, 256, 1, int(T * 0.8), 1 / 1.25, args.steps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

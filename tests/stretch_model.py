@@ -28,6 +28,22 @@ def find_peaks(mag):
     return (np.nonzero(pk)[0] + 2).tolist()
 
 
+def doubtful_frame(mag, ulps=2):
+    """True when a findPeaks comparison of the frame lies within `ulps` f32 ulps of a tie, or a magnitude is NaN: another correctly rounded transform
+    may find other peaks there.  (Introspection for the tests; the model's output does not depend on it.)"""
+    mag = np.asarray(mag, np.float32)
+    if np.any(np.isnan(mag)):
+        return True
+    H = mag.shape[0]
+    if H < 5:
+        return False
+    for a, b in ((mag[1:H - 2], mag[2:H - 1]), (mag[0:H - 2], mag[2:H])):        # the (k, k +- 1) and (k, k +- 2) pairs of k in [2, H - 2)
+        tol = ulps * np.spacing(np.maximum(np.abs(a), np.abs(b)))
+        if np.any(np.abs(a.astype(np.float64) - b.astype(np.float64)) <= tol):
+            return True
+    return False
+
+
 def regions(peaks, H):
     """P[k]: the peak whose region of influence (shiftPeaks at f = 1) holds bin k; -1 everywhere when there is no peak."""
     P = np.full(H, -1, np.int64)
@@ -64,7 +80,7 @@ def phase_advance(q, phi, k, N, ha, hs):
 class StretchModel:
     """One pv_stretch handle with `nch` channel slots."""
 
-    def __init__(self, N, ha, hs, nch=1):
+    def __init__(self, N, ha, hs, nch=1, track_doubt=False):
         if N < 2 or N & (N - 1):
             raise ValueError("FFT size must be a power of two and bigger than 1")
         if not (1 <= ha <= N) or not (1 <= hs <= N // 2):
@@ -77,6 +93,10 @@ class StretchModel:
         self.acc = np.zeros((nch, N - hs), np.float32)
         self.phi = np.zeros((nch, self.H), np.uint32)
         self.psi = np.zeros((nch, self.H), np.uint32)
+        self.last = None                                 # introspection: the last frame's X, mag, q, peaks, adv (see frame)
+        self.track_doubt = track_doubt
+        self.doubtful = [[] for _ in range(nch)]         # per channel, per frame (track_doubt only): doubtful_frame(mag)
+        self.cond_min = np.full((nch, self.H), np.inf)   # per channel (track_doubt only): min over frames of |X_k| / max |X|
 
     def frame(self, c, block):
         """One frame of channel c: `ha` new samples in, `hs` samples out."""
@@ -91,6 +111,11 @@ class StretchModel:
         adv = phase_advance(q, self.phi[c], self.k, N, ha, hs)
         self.psi[c] = ((self.psi[c].astype(np.uint64) + adv) & MASK).astype(np.uint32)
         self.phi[c] = q
+        self.last = {"X": X, "mag": mag, "q": q, "peaks": P, "adv": adv}
+        if self.track_doubt:
+            self.doubtful[c].append(doubtful_frame(mag))
+            ax = np.abs(X)
+            self.cond_min[c] = np.minimum(self.cond_min[c], ax / ax.max() if ax.max() > 0 else 0.0)
         if P[0] < 0:
             Y = np.zeros(self.H, np.complex128)                                         # no peaks: silence, as the pitch shifter
         else:

@@ -32,10 +32,10 @@ def _signal(nch, n):
     return np.stack([S.make_signal("tonal" if c % 2 == 0 else "noise", c, n) for c in range(nch)])
 
 
-@pytest.mark.parametrize("N", [256, 1024, 2048, 4096, 8192])
+@pytest.mark.parametrize("N", [256, 512, 1024, 2048, 4096, 8192])
 @pytest.mark.parametrize("ratio", [0.5, 0.8, 1.25, 2.0])
 @pytest.mark.parametrize("nch", [1, 8])
-def test_model_parity(N, ratio, nch):
+def test_model_parity(N, ratio, nch, record_property):
     import phaze_amd
     ha, hs = _hops(N, ratio)
     assert abs(hs / ha - ratio) < 1e-9
@@ -46,8 +46,9 @@ def test_model_parity(N, ratio, nch):
     ts.close()
     ref = StretchModel(N, ha, hs, nch).process(x)
     assert y.shape == ref.shape == (nch, T * hs)
-    for c in range(nch):
-        assert _rel(y[c], ref[c]) <= 1e-5, (c, _rel(y[c], ref[c]))
+    worst = max(_rel(y[c], ref[c]) for c in range(nch))
+    record_property("rel", worst)
+    assert worst <= 5e-7, worst                                       # measured <= 1.3e-7 on one MI355X
 
 
 @pytest.mark.parametrize("N,hop", [(1024, 256), (2048, 128)])

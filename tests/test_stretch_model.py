@@ -1,11 +1,15 @@
 """CPU checks of the time-stretch model (tests/stretch_model.py) that the GPU kernels are held to: at ha = hs it is the pitch shifter at pitchFactor 1
 (the path pinned to the reference), a stretched sine keeps its frequency, and the fixed-point phase advance is the integer arithmetic of DESIGN.md."""
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
 import oracle_lib
 import signals as S
+import tones as TN
 from stretch_model import StretchModel, phase_advance, phase_q, regions, find_peaks
+from tones import edge_d, phi_for_d
 
 
 def _rel(a, b):
@@ -64,3 +68,70 @@ def test_regions_follow_shift_peaks_at_one():
     assert regions([3, 8, 12], 16).tolist() == [3] * 6 + [8] * 4 + [12] * 6
     mag = np.array([0, 1, 5, 1, 0, 2, 3, 9, 2], np.float32)
     assert find_peaks(mag) == [2]                                    # i in [2, H - 2): bin 7 is outside
+
+
+# ---- a closed-form oracle: stationary tones (tests/tones.py) -------------------------------------------------------------------------------------------
+# What the model gives (max |amplitude ratio - 1| / residual): single tones <= 2e-8 / <= 7e-7, two partials 3e-7 / 2.4e-5, three partials 5e-9 / 3.5e-6.
+# The gates are about 4x that; the multi-partial residual is the algorithm's (the other partial's window sidelobes locked to the wrong peak), not rounding.
+CPU_TOL = {"2p-1024-256-320": 1e-4, "3p-1024-256-384": 1.5e-5}
+
+
+@pytest.mark.parametrize("cid", list(TN.CASES))
+def test_tones_closed_form(cid):
+    N, ha, hs, freqs, amps = TN.CASES[cid]
+    TN.check_partials(N, freqs)
+    T, x = TN.case_input(N, ha, hs, freqs, amps)
+    y = StretchModel(N, ha, hs).process(x[None, :])[0]
+    ratio, res = TN.tone_fit(y, N, ha, hs, freqs, amps)
+    tol = CPU_TOL.get(cid, 3e-6)
+    assert np.all(np.abs(ratio - 1.0) <= tol), (ratio, tol)
+    assert res <= tol, (res, tol)
+
+
+def test_envelope_ripple():
+    """g(n) is what a correct vocoder's gain is: 0.25 .. 0.5 at R_s = 2, +-0.8 % at R_s = 3.2, +-4.3 % at R_s = 8/3, flat at R_s = 4 and 8."""
+    lo, hi = TN.ripple(1024, 512)
+    assert abs(lo - 0.25) < 1e-9 and abs(hi - 0.5) < 1e-9
+    for hs, rip in ((320, 0.008), (384, 0.043)):
+        lo, hi = TN.ripple(1024, hs)
+        assert abs((hi - lo) / (hi + lo) - rip) < 0.001, (hs, lo, hi)
+    for hs in (256, 128):
+        lo, hi = TN.ripple(1024, hs)
+        assert hi - lo < 1e-6 and abs(hi - 0.375) < 1e-6
+
+
+def test_half_bin_tie_is_silent():
+    """A tone on an exact half bin has two equal bins in exact arithmetic.  Where they tie, there is no strict maximum: findPeaks finds no peak and the frame
+    is silent (the reference's rule).  Whether they tie rests on the rounding of the input, so the tone tests keep 0.05 bin away from a half bin."""
+    mag = np.array([0, 1, 3, 9, 9, 3, 1, 0, 0], np.float32)
+    assert find_peaks(mag) == []
+    assert regions(find_peaks(mag), mag.size).tolist() == [-1] * mag.size
+    m = StretchModel(256, 64, 80)
+    assert np.all(m.process(np.zeros((1, 8 * 64), np.float32)) == 0.0) and m.last["peaks"][0] == -1
+
+
+def _adv_exact(q, phi, k, N, ha, hs):
+    """The advance from its definition with Python integers: hs k 2^32/N + round-half-up(d hs / ha), d the principal value of q - phi - ha k 2^32/N."""
+    out = []
+    for qq, pp, kk in zip(q.tolist(), phi.tolist(), k.tolist()):
+        d = (qq - pp - ha * kk * (2 ** 32 // N)) % 2 ** 32
+        d = d - 2 ** 32 if d >= 2 ** 31 else d
+        r = (2 * d * hs + ha) // (2 * ha)                        # floor(d hs / ha + 1/2)
+        assert Fraction(r) <= Fraction(d * hs, ha) + Fraction(1, 2) < r + 1
+        out.append((hs * kk * (2 ** 32 // N) + r) % 2 ** 32)
+    return out
+
+
+@pytest.mark.parametrize("N,ha,hs", [(1024, 256, 384), (8192, 1, 4096), (256, 256, 1), (512, 100, 97), (256, 255, 64), (1024, 7, 8)])
+def test_fixed_point_advance_edges(N, ha, hs):
+    """phase_advance at the edges of d: -2^31, 2^31 - 1, 0, +-1, the d where 2 d hs + ha sits on (or just below) a multiple of 2 ha, random d."""
+    rng = np.random.default_rng(N + ha + hs)
+    H = N // 2 + 1
+    k = np.arange(H, dtype=np.int64)
+    q = rng.integers(0, 2 ** 32, H, dtype=np.uint64).astype(np.uint32)
+    d = edge_d(ha, hs, H, rng)
+    phi = phi_for_d(q, d, k, N, ha)
+    got = phase_advance(q, phi, k, N, ha, hs).tolist()
+    assert got == _adv_exact(q, phi, k, N, ha, hs)
+    # and at those bins the rounding really is on an edge (ha > 1): floor(... + 1/2) with and without the half differ somewhere
+    assert ha == 1 or any(((2 * int(dd) * hs + ha) // (2 * ha)) != ((2 * int(dd) * hs) // (2 * ha)) for dd in d)

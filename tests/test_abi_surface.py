@@ -74,6 +74,30 @@ def test_errors_without_device():
             phaze_amd.PhaseVocoder(fft_size=1024, hop_size=256)
 
 
+def test_generic_kernel_lds_boundary_at_8192():
+    """PV_FLAG_GENERIC_KERNEL at N = 8192: 16 (N/2 + 1) + 8 N + 4 (N - hop) + 16 * 65 bytes of LDS.  hop 256 needs 163 872 B and is refused before any
+    device is touched; hop 512 needs 162 848 B, inside the 163 328 B allowed, and passes validation (without a device it then fails for the device
+    alone).  Without the flag, hop 256 runs the LDS ring of pv_wg_kernel and passes validation too."""
+    from phaze_amd import capi
+    L = _lib()
+    h = C.c_void_p()
+    cfg = capi.make_config(8192, 256, flags=capi.FLAG_GENERIC_KERNEL)
+    assert L.pv_create(C.byref(cfg), C.byref(h)) == capi.PV_ERR_UNSUPPORTED
+    assert "LDS" in L.pv_last_error(None).decode()
+    try:
+        import torch
+        has_gpu = torch.cuda.is_available()
+    except Exception:
+        has_gpu = False
+    for hop, flags in ((512, capi.FLAG_GENERIC_KERNEL), (256, 0)):
+        cfg = capi.make_config(8192, hop, flags=flags)
+        rc = L.pv_create(C.byref(cfg), C.byref(h))
+        if has_gpu:
+            assert rc == capi.PV_OK, (hop, flags, L.pv_last_error(None).decode())
+            L.pv_destroy(h)
+        else:
+            assert rc == capi.PV_ERR_DEVICE, (hop, flags, L.pv_last_error(None).decode())
+
 def test_product_sources_do_not_reference_the_oracle():
     for base, _, files in os.walk(os.path.join(ROOT, "phaze_amd")):
         for f in files:

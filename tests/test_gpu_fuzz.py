@@ -14,7 +14,8 @@ def _case(rng):
     N = 1 << log2n
     hop = N >> int(rng.integers(0, min(log2n - 1, 5) + 1))
     if N == 8192 and hop < 1024:
-        hop = 1024                                   # LDS limit of the generic kernel at 8192 (documented in include/phaze_amd.h)
+        hop = 1024                                   # kept so that the seeds keep their cases: N = 8192 runs every even hop down to 2 (the LDS ring of
+                                                     # pv_wg_kernel); tests/test_gpu_hop_axis.py fuzzes the hops skipped here
     nch = int(rng.integers(1, 4))
     T = int(rng.integers(1, 40 if N <= 2048 else 14))
     kind = ["noise", "tonal"][int(rng.integers(0, 2))]

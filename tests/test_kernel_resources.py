@@ -76,3 +76,38 @@ def test_headline_instances_keep_three_waves_per_simd_and_their_hot_path_out_of_
             assert v["VGPRs Spill"] == 0 and v["ScratchSize"] == 0, (k, v)
         if spread == "1" and f32 == "1":
             assert v["VGPRs Spill"] <= 8, (k, v)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+def test_wg_instances_and_the_lds_ring_keep_their_registers():
+    """pv_wg_kernel: N = 2048 / 4096 / 8192 (G = 2 / 4 / 8 waves), S_ROWS = 8 hop / N for hop >= N/8 and S_ROWS = 0 for the LDS overlap-add ring that
+    runs every smaller hop (R up to N / 2, run-time R).  The ring instances (product and tap) hold a frame in 229..246 VGPRs: two waves per SIMD, no
+    AGPRs, nothing spilled.  The resident instances (N = 8192, hop >= N/8) are not bound by this."""
+    src = os.path.join(ROOT, "phaze_amd", "csrc")
+    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
+                          "-o", os.devnull, "pv_wg_kernel.hip"], cwd=src, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    kernels, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and name:
+            kernels[name][m.group(1).strip()] = int(m.group(2))
+    inst = {k: v for k, v in kernels.items() if "pv_wg_kernel" in k}
+    assert len(inst) == 34, sorted(inst)                         # 3 sizes x 5 row counts (0, 1, 2, 4, 8) x (product, tap) + 4 resident at N = 8192
+    ring = 0
+    for k, v in inst.items():
+        log2n, rows, aux, resident = re.search(r"ILi(\d+)ELi(\d+)ELb([01])ELb([01])E", k).groups()
+        assert v["LDS Size"] == 256, (k, v)                     # static LDS: what the dispatch tests add to the dynamic size
+        if resident == "1":
+            assert log2n == "13" and rows != "0", k
+            continue
+        assert v["Occupancy"] == 2 and v["AGPRs"] == 0 and v["VGPRs"] <= 256, (k, v)
+        if rows == "0":
+            ring += 1
+            assert v["VGPRs Spill"] == 0, (k, v)
+    assert ring == 6                                             # 3 sizes x (product, tap)

@@ -49,7 +49,8 @@ typedef struct pv_handle pv_handle;
  *     pv_reset_channels_part + PV_FLAG_HOST_CHANNEL_BOOKKEEPING;
  * 4 = round 5: PV_FLAG_FP64_FORWARD, pv_forward_stats;
  * 5 = round 6: PV_FLAG_TEST_FAIL_SECOND_PIECE (a test hook); no layout or semantic change of anything that existed;
- * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed. */
+ * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed.  Later, still 6 (additive: new symbols only, no
+ *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -291,6 +292,24 @@ PV_API int pv_stretch_synchronize(pv_stretch *h);
 PV_API int pv_stretch_export_state(pv_stretch *h, int32_t ch, float *hist, float *acc, uint32_t *phi, uint32_t *psi);
 PV_API int pv_stretch_import_state(pv_stretch *h, int32_t ch, const float *hist, const float *acc,
                                    const uint32_t *phi, const uint32_t *psi);
+
+/* ---- variable tempo on a time-stretch handle: a per-frame analysis hop ------------------------------------------------------------- */
+/* Frame m of channel slot c consumes hops[c * hop_stride + m] input samples (hop_stride == 0: every channel uses row 0) and emits synthesis_hop
+ * output samples; its window is the newest N samples of the stream, and its hop takes the place of analysis_hop in the phase advance.  The
+ * handle's analysis_hop is the FLOOR: every hop must lie in [analysis_hop, N] (the state keeps N - analysis_hop samples of history, all a hop
+ * >= the floor needs; create the handle with analysis_hop = 1 for the widest range).  Channel c reads in[c*in_stride .. + sum of its row) and
+ * writes out[c*out_stride .. + nframes*hs).  pv_stretch_process is this call with every hop equal to the floor: the two may be mixed on one handle,
+ * and any split of a schedule into calls gives the same bits.
+ * `hops` is a HOST array in both forms, read before the call returns (it may be reused at once, also after the asynchronous device form).
+ * Rejected with PV_ERR_ARGUMENT before any device work, processing nothing and leaving the state untouched: a null buffer, negative counts, a null
+ * hops with nframes > 0, a hop_stride that is neither 0 nor >= nframes, a hop outside [analysis_hop, N] (the message names its channel and frame),
+ * and with nch > 1 an in_stride below the largest row total or an out_stride below nframes*hs.  nch > max_channels: PV_ERR_CAPACITY.
+ * Host pointers, synchronous: staged in pieces of at most max_frames frames (and what fits the input staging, grown once to one frame of hop N). */
+PV_API int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops,
+                            int64_t hop_stride, int64_t in_stride, int64_t out_stride);
+/* The same on DEVICE in / out pointers, asynchronous on the handle's stream. */
+PV_API int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes,
+                                   const int32_t *hops, int64_t hop_stride, int64_t in_stride, int64_t out_stride);
 
 #ifdef __cplusplus
 }

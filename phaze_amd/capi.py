@@ -25,6 +25,7 @@ EXPORTS = [
     "pv_forward_stats",
     "pv_stretch_create", "pv_stretch_destroy", "pv_stretch_reset", "pv_stretch_last_error", "pv_stretch_process", "pv_stretch_process_device",
     "pv_stretch_set_stream", "pv_stretch_synchronize", "pv_stretch_export_state", "pv_stretch_import_state",
+    "pv_tempo_process", "pv_tempo_process_device",
 ]
 
 
@@ -134,6 +135,9 @@ def load_library():
     L.pv_stretch_synchronize.argtypes = [vp]
     L.pv_stretch_export_state.argtypes = [vp, C.c_int32, fp, fp, up, up]
     L.pv_stretch_import_state.argtypes = [vp, C.c_int32, fp, fp, up, up]
+    ip = C.POINTER(C.c_int32)
+    L.pv_tempo_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_tempo_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -409,6 +413,27 @@ class PhaseVocoder:
         return {"X": X, "mag": mag, "flags": flags, "Y": Y}
 
 
+def tempo_hops(tempo, synthesis_hop, min_hop, max_hop, carry=0.0):
+    """Integer analysis hops for a per-frame tempo (input samples per output sample: 1.25 plays 25 % faster), by error diffusion:
+    hop_m = round(carry + tempo_m * synthesis_hop), the remainder carried on.  After every frame the input consumed, sum(hops), is within half a
+    sample of carry + sum(tempo * synthesis_hop).  Every tempo_m * synthesis_hop must lie in [min_hop, max_hop] (a TimeStretch's analysis_hop and
+    fft_size).  Returns (int32[nframes] hops, carry); continuing with the returned carry gives the hops of one call over the whole tempo track."""
+    t = np.atleast_1d(np.asarray(tempo, np.float64))
+    if t.ndim != 1:
+        raise ValueError("tempo must be a scalar or one value per frame")
+    want = t * synthesis_hop
+    if not (min_hop <= max_hop) or np.any(~np.isfinite(want)) or np.any(want < min_hop) or np.any(want > max_hop):
+        raise ValueError(f"tempo * synthesis_hop must lie in [{min_hop}, {max_hop}]")
+    hops = np.empty(t.size, np.int32)
+    e = float(carry)
+    for m, w in enumerate(want.tolist()):
+        x = e + w
+        h = min(max(int(np.floor(x + 0.5)), min_hop), max_hop)
+        hops[m] = h
+        e = x - h
+    return hops, e
+
+
 class TimeStretch:
     """Phase-locked time stretch (pv_stretch_*): tempo change at constant pitch.  Each frame consumes `analysis_hop` input samples and emits
     `synthesis_hop` output samples, so the output lasts synthesis_hop / analysis_hop times as long; it lags the input by fft_size - synthesis_hop
@@ -463,6 +488,49 @@ class TimeStretch:
     def process_device(self, d_in, d_out, nch, nframes, in_stride, out_stride):
         """Raw device pointers (ints).  Asynchronous on the handle's stream."""
         self._check(self._L.pv_stretch_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, in_stride, out_stride))
+
+    @staticmethod
+    def _hop_rows(hops):
+        """(int32 array, nframes, hop_stride): a 1-D schedule is one row for every channel, a 2-D one [nch, nframes] a row per channel."""
+        hops = np.ascontiguousarray(hops, dtype=np.int32)
+        if hops.ndim == 1:
+            return hops, hops.size, 0
+        if hops.ndim != 2:
+            raise ValueError("hops must be int[nframes] or int[nch, nframes]")
+        return hops, hops.shape[1], hops.shape[1]
+
+    def process_hops(self, x, hops):
+        """Variable tempo (pv_tempo_process): frame m of channel c consumes hops[m] (1-D) or hops[c, m] (2-D) input samples, each in
+        [analysis_hop, fft_size], and emits synthesis_hop samples.  x: float32[nch, n] (host), n == hops.sum() for a 1-D schedule, n >= the largest
+        row sum for a 2-D one (each row reads its own prefix) -> float32[nch, nframes * synthesis_hop]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        h, nframes, stride = self._hop_rows(hops)
+        if h.ndim == 1 and int(h.astype(np.int64).sum()) != n:
+            raise ValueError(f"the input holds {n} samples per channel, the schedule consumes {int(h.astype(np.int64).sum())}")
+        if h.ndim == 2:
+            if h.shape[0] != nch:
+                raise ValueError(f"{h.shape[0]} schedule rows for {nch} channels")
+            if nframes and int(h.astype(np.int64).sum(axis=1).max()) > n:
+                raise ValueError("the input is shorter than a row of the schedule consumes")
+        y = np.empty((nch, nframes * self.synthesis_hop), np.float32)
+        if nch and nframes:
+            self._check(self._L.pv_tempo_process(self._h, _fp(x), _fp(y), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)), stride, n,
+                                                 nframes * self.synthesis_hop))
+        return y
+
+    def process_hops_device(self, d_in, d_out, nch, nframes, hops, in_stride, out_stride):
+        """pv_tempo_process_device on raw device pointers (ints), asynchronous on the handle's stream.  hops: host int[nframes] (shared) or int[nch, >= nframes];
+        the library has read it when this returns."""
+        h, _, stride = self._hop_rows(hops)
+        if h.ndim == 1 and h.size != nframes:
+            raise ValueError(f"{h.size} hops for {nframes} frames")
+        if h.ndim == 2 and h.shape[0] < nch:
+            raise ValueError(f"{h.shape[0]} schedule rows for {nch} channels")
+        self._check(self._L.pv_tempo_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    stride, in_stride, out_stride))
 
     def set_stream(self, hip_stream):
         self._check(self._L.pv_stretch_set_stream(self._h, C.c_void_p(hip_stream)))

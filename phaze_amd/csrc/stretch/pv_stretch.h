@@ -7,11 +7,11 @@
 inline long pv_stretch_state_stride(int N, int ha, int hs) { return (long)(N - ha) + (N - hs) + 2L * (N / 2 + 1); }
 
 struct PvStretchParams {
-    const float *in;          // channel c at in + c * in_stride: nframes * ha samples
+    const float *in;          // channel c at in + c * in_stride: nframes * ha samples (with pos: pos[c * pos_stride + nframes] samples)
     float *out;               // channel c at out + c * out_stride: nframes * hs samples
     long in_stride, out_stride;
     int nframes, nch;
-    int ha, hs;
+    int ha, hs;               // ha: the analysis hop, or with pos the floor of the scheduled hops (hist holds N - ha samples either way)
     int F;                    // frames per chain (>= halo + 1 whenever there is more than one chain)
     int nchains;              // chains per channel
     int halo;                 // (N - 1) / hs: earlier frames that overlap a frame's first output sample
@@ -23,6 +23,9 @@ struct PvStretchParams {
     const double2 *tw64;      // exp(-2 pi j k / N), k in [0, N)
     const float2 *tw32;
     const float *hann;        // periodic Hann, f32, N values
+    const long long *pos;     // variable tempo: [rows][nframes + 1] input consumed before frame m, S[0] = 0, S[m + 1] - S[m] = frame m's hop in [ha, N];
+                              // frame m's window is stream[S[m + 1] - ha, + N).  nullptr: S[m] = m ha (the fixed-hop kernels)
+    long pos_stride;          // int64 per row of pos (0: one row shared by every channel)
 };
 
 bool pv_stretch_supported(int log2n);                     // N = 256 .. 8192

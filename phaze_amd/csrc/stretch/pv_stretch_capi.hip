@@ -2,12 +2,14 @@
 //
 // Owns one time-stretch handle's device state -- per channel slot hist[N - ha] | acc[N - hs] | phi[H] | psi[H] (pv_stretch.h) -- and turns calls
 // into pass A + scan + pass B launches (pv_stretch_kernels.hip).  No CPU compute path: without a HIP device pv_stretch_create fails with PV_ERR_DEVICE.
+// pv_tempo_process / pv_tempo_process_device (variable tempo) turn a host schedule of per-frame hops into the kernels' position table.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../../include/phaze_amd.h"
@@ -31,6 +33,11 @@ struct pv_stretch {
     unsigned *d_sums;            // pass A / scan / pass B exchange, grown on demand
     size_t sums_cap;             // (in u32 words)
     float *d_stage_in, *d_stage_out;   // host-pointer calls: max_channels x max_frames frames
+    long stage_in_pitch;         // floats per channel of d_stage_in: max_frames * ha, or N once a tempo call needed one frame of hop N to fit
+    long long *d_pos, *h_pos;    // variable tempo: the position table on the device, and its page-locked upload buffer (grown on demand)
+    size_t pos_cap, hpos_cap;    // (in int64 words)
+    hipEvent_t pos_done;         // recorded behind the last upload: h_pos may be rewritten once it has completed
+    bool pos_pending;
     char err[256];
 };
 
@@ -74,8 +81,10 @@ int pick_chain(const pv_stretch *h, int nch, int nframes)
     return (int)F;
 }
 
-// One launch over channel slots [0, nch): device pointers, asynchronous on h->stream.
-int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, long in_stride, long out_stride)
+// One launch over channel slots [0, nch): device pointers, asynchronous on h->stream.  d_pos: the position table of a tempo call (pv_stretch.h), or
+// nullptr for the fixed hop.
+int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, long in_stride, long out_stride, const long long *d_pos = nullptr,
+        long pos_stride = 0)
 {
     PvStretchParams p;
     memset(&p, 0, sizeof p);
@@ -87,6 +96,7 @@ int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, lo
     p.ola_scale = (float)((double)h->hs / (double)h->N);
     p.state_in = h->d_state; p.state_out = h->d_state_out; p.state_stride = h->stride;
     p.tw64 = h->d_tw64; p.tw32 = h->d_tw32; p.hann = h->d_hann;
+    p.pos = d_pos; p.pos_stride = pos_stride;
     const size_t words = (size_t)nch * (size_t)p.nchains * 2 * (size_t)h->H;
     if (words > h->sums_cap) {
         SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still use the old buffer
@@ -108,6 +118,78 @@ int check_call(pv_stretch *h, const void *in, const void *out, int32_t nch, int3
     if (nch > h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_process: more channels than max_channels");
     if (nch > 1 && (in_stride < (int64_t)nframes * h->ha || out_stride < (int64_t)nframes * h->hs))
         return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: channel strides shorter than nframes * hop");
+    return PV_OK;
+}
+
+// ---- variable tempo ----
+
+// Everything a tempo call may reject, before any device work.  tot[r]: the input total of schedule row r (nrows = 1 for a shared row, else nch).
+int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                int64_t in_stride, int64_t out_stride, std::vector<long long> &tot)
+{
+    char msg[256];
+    if (!in || !out) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
+    if (nframes > 0 && !hops) { snprintf(msg, sizeof msg, "%s: null hops", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (hop_stride != 0 && hop_stride < nframes) {
+        snprintf(msg, sizeof msg, "%s: hop_stride %lld is neither 0 (one row for every channel) nor >= nframes %d", fn, (long long)hop_stride, nframes);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
+    const int nrows = hop_stride == 0 ? 1 : nch;
+    tot.assign((size_t)nrows, 0);
+    long long most = 0;
+    for (int r = 0; r < nrows && nframes > 0; r++) {
+        const int32_t *row = hops + (size_t)r * (size_t)hop_stride;
+        long long t = 0;
+        for (int m = 0; m < nframes; m++) {
+            if (row[m] < h->ha || row[m] > h->N) {
+                snprintf(msg, sizeof msg, "%s: hop %d of channel %d, frame %d is outside [analysis_hop %d, fft_size %d]", fn, (int)row[m], r, m, h->ha, h->N);
+                return sfail(h, PV_ERR_ARGUMENT, msg);
+            }
+            t += row[m];
+        }
+        tot[(size_t)r] = t;
+        if (t > most) most = t;
+    }
+    if (nch > 1 && (in_stride < most || out_stride < (int64_t)nframes * h->hs)) {
+        snprintf(msg, sizeof msg, "%s: channel strides shorter than the largest row's input (%lld) or nframes * synthesis_hop (%lld)", fn, most,
+                 (long long)nframes * h->hs);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
+    return PV_OK;
+}
+
+// Frames [f0, f0 + nf) of every row as a position table, S[r][i] = sum of hops f0 .. f0 + i - 1 of row r, uploaded on h->stream into h->d_pos.
+// The page-locked h_pos is rewritten only once the previous upload has completed, so a device call may follow another before any synchronise.
+int upload_pos(pv_stretch *h, const int32_t *hops, int64_t hop_stride, int nrows, int f0, int nf)
+{
+    const size_t words = (size_t)nrows * (size_t)(nf + 1);
+    if (h->pos_pending) SCHK(h, hipEventSynchronize(h->pos_done));
+    h->pos_pending = false;
+    if (words > h->hpos_cap) {
+        if (h->h_pos) (void)hipHostFree(h->h_pos);
+        h->h_pos = nullptr; h->hpos_cap = 0;
+        SCHK(h, hipHostMalloc((void **)&h->h_pos, words * sizeof(long long), hipHostMallocDefault));
+        h->hpos_cap = words;
+    }
+    if (words > h->pos_cap) {
+        SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still read the old table
+        if (h->d_pos) (void)hipFree(h->d_pos);
+        h->d_pos = nullptr; h->pos_cap = 0;
+        SCHK(h, hipMalloc(&h->d_pos, words * sizeof(long long)));
+        h->pos_cap = words;
+    }
+    if (!h->pos_done) SCHK(h, hipEventCreateWithFlags(&h->pos_done, hipEventDisableTiming));
+    for (int r = 0; r < nrows; r++) {
+        const int32_t *row = hops + (size_t)r * (size_t)hop_stride + f0;
+        long long *S = h->h_pos + (size_t)r * (size_t)(nf + 1);
+        S[0] = 0;
+        for (int i = 0; i < nf; i++) S[i + 1] = S[i] + row[i];
+    }
+    SCHK(h, hipMemcpyAsync(h->d_pos, h->h_pos, words * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipEventRecord(h->pos_done, h->stream));
+    h->pos_pending = true;
     return PV_OK;
 }
 
@@ -187,6 +269,7 @@ int pv_stretch_create(const pv_stretch_config *cfg, pv_stretch **out)
     CCHK(hipMalloc(&h->d_state_out, state));
     CCHK(hipMemset(h->d_state, 0, state));
     CCHK(hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)maxch * (size_t)maxfr * ha));
+    h->stage_in_pitch = (long)maxfr * ha;
     CCHK(hipMalloc(&h->d_stage_out, sizeof(float) * (size_t)maxch * (size_t)maxfr * hs));
 #undef CCHK
     *out = h;
@@ -199,9 +282,11 @@ int pv_stretch_destroy(pv_stretch *h)
     if (!slive(h)) return PV_ERR_DESTROYED;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    void *ptrs[] = {h->d_tw64, h->d_tw32, h->d_hann, h->d_state, h->d_state_out, h->d_sums, h->d_stage_in, h->d_stage_out};
+    if (h->pos_done) (void)hipEventDestroy(h->pos_done);
+    void *ptrs[] = {h->d_tw64, h->d_tw32, h->d_hann, h->d_state, h->d_state_out, h->d_sums, h->d_stage_in, h->d_stage_out, h->d_pos};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->h_pos) (void)hipHostFree(h->h_pos);
     (void)hipGetLastError();
     h->magic = 0;
     free(h);
@@ -262,6 +347,74 @@ int pv_stretch_process(pv_stretch *h, const float *in, float *out, int32_t nch, 
         SCHK(h, hipMemcpy2DAsync(out + (long)f0 * h->hs, opitch, h->d_stage_out, sizeof(float) * sout,
                                  sizeof(float) * (size_t)nf * h->hs, nch, hipMemcpyDeviceToHost, h->stream));
         SCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PV_OK;
+}
+
+int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                            int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<long long> tot;
+    const int rc = check_tempo(h, "pv_tempo_process_device", d_in, d_out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    const int nrows = hop_stride == 0 ? 1 : nch;
+    const int r = upload_pos(h, hops, hop_stride, nrows, 0, nframes);
+    if (r != PV_OK) return r;
+    return run(h, d_in, d_out, nch, nframes, (long)in_stride, (long)out_stride, h->d_pos, hop_stride == 0 ? 0 : (long)nframes + 1);
+}
+
+int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                     int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<long long> tot;
+    const int rc = check_tempo(h, "pv_tempo_process", in, out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    if (h->stage_in_pitch < h->N) {                                    // max_frames * ha < N: one frame of hop N must fit a piece
+        SCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_stage_in);
+        h->d_stage_in = nullptr;
+        SCHK(h, hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)h->max_channels * (size_t)h->N));
+        h->stage_in_pitch = h->N;
+    }
+    // pieces of at most max_frames frames whose every row fits the input staging; each channel row is copied over exactly its own span
+    const int nrows = hop_stride == 0 ? 1 : nch;
+    const long sin = h->stage_in_pitch, sout = (long)h->max_frames * h->hs;
+    const size_t opitch = sizeof(float) * (size_t)(nch > 1 ? out_stride : (int64_t)nframes * h->hs);
+    std::vector<long long> at((size_t)nrows, 0), span((size_t)nrows);    // per row: input consumed before the piece, and the piece's own
+    for (int f0 = 0; f0 < nframes;) {
+        int nf = 0;
+        std::fill(span.begin(), span.end(), 0LL);
+        while (nf < h->max_frames && f0 + nf < nframes) {               // the first frame always fits: hop <= N <= sin
+            bool fits = true;
+            for (int r = 0; r < nrows && fits; r++) fits = span[(size_t)r] + hops[(size_t)r * (size_t)hop_stride + f0 + nf] <= sin;
+            if (!fits) break;
+            for (int r = 0; r < nrows; r++) span[(size_t)r] += hops[(size_t)r * (size_t)hop_stride + f0 + nf];
+            nf++;
+        }
+        if (nrows == 1) {
+            const size_t ipitch = sizeof(float) * (size_t)(nch > 1 ? in_stride : tot[0]);
+            SCHK(h, hipMemcpy2DAsync(h->d_stage_in, sizeof(float) * sin, in + at[0], ipitch, sizeof(float) * (size_t)span[0], nch,
+                                     hipMemcpyHostToDevice, h->stream));
+        } else {
+            for (int c = 0; c < nch; c++)
+                SCHK(h, hipMemcpyAsync(h->d_stage_in + (size_t)c * sin, in + (size_t)c * (size_t)in_stride + at[(size_t)c], sizeof(float) * (size_t)span[(size_t)c],
+                                       hipMemcpyHostToDevice, h->stream));
+        }
+        int r = upload_pos(h, hops, hop_stride, nrows, f0, nf);
+        if (r != PV_OK) return r;
+        r = run(h, h->d_stage_in, h->d_stage_out, nch, nf, sin, sout, h->d_pos, hop_stride == 0 ? 0 : (long)nf + 1);
+        if (r != PV_OK) return r;
+        SCHK(h, hipMemcpy2DAsync(out + (long)f0 * h->hs, opitch, h->d_stage_out, sizeof(float) * sout,
+                                 sizeof(float) * (size_t)nf * h->hs, nch, hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        for (int rr = 0; rr < nrows; rr++) at[(size_t)rr] += span[(size_t)rr];
+        f0 += nf;
     }
     return PV_OK;
 }

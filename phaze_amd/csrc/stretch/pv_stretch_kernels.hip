@@ -10,6 +10,8 @@
 //   pass B  the chain again from its carry, `halo` frames early for the overlap-add (their psi is the carry minus their adv sum: exact mod 2^32);
 //           locks, inverts, overlap-adds and stores; the last chain of a channel writes the carried state
 // Every carried quantity is an integer sum or a per-frame function of the input, so any split of a stream into calls or chains gives the same bits.
+// Variable tempo (SCHED): frame m consumes its own hop ha_m >= ha and its window ends at the input consumed so far, S[m + 1]; positions and hops come
+// from the host's prefix table (PvStretchParams::pos).  The fixed-hop instances (SCHED = false) compute S[m] = m ha and never read a table.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -35,13 +37,30 @@ struct SC {
     static constexpr size_t LDS_B = A_BYTES + 3 * H4 + (size_t)N * 4 + 2 * TPB * 4;        // A | mag / P | phi | psi | ring[N] | scan[2][TPB]
 };
 
-// Sample s of the stream "carried history (N - ha) ++ this call's input"; frame m's window is stream[m ha, m ha + N).
+// Sample s of the stream "carried history (N - ha) ++ this call's input"; frame m's window is stream[m ha, m ha + N) (SCHED: Sched::start).
 struct Src {
     const float *hist;
     const float *in;
     long hl;
     __device__ __forceinline__ float at(long s) const { return s < hl ? hist[s] : in[s - hl]; }
 };
+
+// Where frames sit in the stream.  end(n) = S[n], the input consumed by frames 0 .. n-1; frame m's window starts at S[m + 1] - ha (the newest N samples
+// once its hop is in: hist is N - ha long) and its hop is S[m + 1] - S[m].  Wave-uniform: the table reads are scalar loads.
+template <bool SCHED>
+struct Sched {
+    const long long *S;       // this channel's row (SCHED only)
+    int ha;
+    __device__ __forceinline__ long end(int n) const { return SCHED ? (long)S[n] : (long)n * ha; }
+    __device__ __forceinline__ long start(int m) const { return SCHED ? (long)S[m + 1] - ha : (long)m * ha; }
+    __device__ __forceinline__ int hop(int m) const { return SCHED ? (int)(S[m + 1] - S[m]) : ha; }
+};
+
+template <bool SCHED>
+__device__ __forceinline__ Sched<SCHED> sched(const PvStretchParams &p, int c)
+{
+    return Sched<SCHED>{SCHED ? p.pos + (long)c * p.pos_stride : nullptr, p.ha};
+}
 
 // X[0 .. M] (double2) of the Hann-windowed frame starting at stream sample s0.  Radix-2 DIT on z[n] = x[2n] + j x[2n+1], then the real split.
 template <int LOG2N>
@@ -121,7 +140,7 @@ __device__ __forceinline__ float2 rotate(double2 X, int p, const unsigned *psi, 
     return float2{__fsub_rn(__fmul_rn(xr, cs), __fmul_rn(xi, sn)), __fadd_rn(__fmul_rn(xr, sn), __fmul_rn(xi, cs))};
 }
 
-template <int LOG2N>
+template <int LOG2N, bool SCHED>
 __global__ __launch_bounds__(TPB) void pv_stretch_pass_a(PvStretchParams p)
 {
     using C = SC<LOG2N>;
@@ -134,24 +153,26 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_a(PvStretchParams p)
     const long hl = C::N - p.ha;
     const float *st = p.state_in + (long)c * p.state_stride;
     const Src src{st, p.in + (long)c * p.in_stride, hl};
+    const Sched<SCHED> sc = sched<SCHED>(p, c);
     const int m0 = j * p.F, m1 = min(m0 + p.F, p.nframes);
     const int b = j == 0 ? 0 : m0 - p.halo;
     if (j == 0) {
         const unsigned *phi_state = (const unsigned *)(st + hl + (C::N - p.hs));
         for (int k = tid; k < C::H; k += TPB) phi[k] = phi_state[k];
     } else {
-        forward<LOG2N>(A, src, (long)(b - 1) * p.ha, p.hann, p.tw64);
+        forward<LOG2N>(A, src, sc.start(b - 1), p.hann, p.tw64);
         for (int k = tid; k < C::H; k += TPB) phi[k] = phase_q(A[k]);
         __syncthreads();
     }
     for (int k = tid; k < C::H; k += TPB) { sm[k] = 0u; sh[k] = 0u; }
 #pragma unroll 1
     for (int m = b; m < m1; m++) {
-        forward<LOG2N>(A, src, (long)m * p.ha, p.hann, p.tw64);
+        forward<LOG2N>(A, src, sc.start(m), p.hann, p.tw64);
         const bool main_frame = m >= m0;
+        const int ha = sc.hop(m);
         for (int k = tid; k < C::H; k += TPB) {
             const unsigned q = phase_q(A[k]);
-            const unsigned adv = advance<LOG2N>(q, phi[k], k, p.ha, p.hs);
+            const unsigned adv = advance<LOG2N>(q, phi[k], k, ha, p.hs);
             phi[k] = q;
             if (main_frame) sm[k] += adv; else sh[k] += adv;
         }
@@ -179,7 +200,7 @@ __global__ __launch_bounds__(TPB) void pv_stretch_scan(PvStretchParams p, int N)
     ((unsigned *)(p.state_out + (long)c * p.state_stride + off))[k] = psi;
 }
 
-template <int LOG2N>
+template <int LOG2N, bool SCHED>
 __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
 {
     using C = SC<LOG2N>;
@@ -197,6 +218,7 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
     const long hl = N - p.ha;
     const float *st = p.state_in + (long)c * p.state_stride;
     const Src src{st, p.in + (long)c * p.in_stride, hl};
+    const Sched<SCHED> sc = sched<SCHED>(p, c);
     const int m0 = j * p.F, m1 = min(m0 + p.F, p.nframes);
     const int b = j == 0 ? 0 : m0 - p.halo;
     const unsigned *carry = p.sums + (size_t)(c * p.nchains + j) * 2 * H + H;
@@ -207,7 +229,7 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
         for (int k = tid; k < H; k += TPB) phi[k] = phi_state[k];
         for (int i = tid; i < N; i += TPB) ring[i] = i < N - p.hs ? acc[i] : 0.0f;
     } else {
-        forward<LOG2N>(A, src, (long)(b - 1) * p.ha, p.hann, p.tw64);
+        forward<LOG2N>(A, src, sc.start(b - 1), p.hann, p.tw64);
         for (int k = tid; k < H; k += TPB) phi[k] = phase_q(A[k]);
         for (int i = tid; i < N; i += TPB) ring[i] = 0.0f;
     }
@@ -217,13 +239,14 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
     const float inv_n = 1.0f / (float)N;
 #pragma unroll 1
     for (int m = b; m < m1; m++) {
-        forward<LOG2N>(A, src, (long)m * p.ha, p.hann, p.tw64);
+        forward<LOG2N>(A, src, sc.start(m), p.hann, p.tw64);
         // magnitudes (computeMagnitudes: re^2 + im^2 in fp64, stored as f32), analysis phase, phase advance
+        const int ha = sc.hop(m);
         for (int k = tid; k < H; k += TPB) {
             const double2 X = A[k];
             mag[k] = (float)__dadd_rn(__dmul_rn(X.x, X.x), __dmul_rn(X.y, X.y));
             const unsigned q = phase_q(X);
-            psi[k] += advance<LOG2N>(q, phi[k], k, p.ha, p.hs);
+            psi[k] += advance<LOG2N>(q, phi[k], k, ha, p.hs);
             phi[k] = q;
         }
         __syncthreads();
@@ -347,7 +370,7 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
     }
     if (j == p.nchains - 1) {
         float *so = p.state_out + (long)c * p.state_stride;
-        const long e = (long)p.nframes * p.ha;
+        const long e = sc.end(p.nframes);
         for (long i = tid; i < hl; i += TPB) so[i] = src.at(e + i);
         for (int i = tid; i < N - p.hs; i += TPB) so[hl + i] = ring[(base + i) & (N - 1)];
         unsigned *sphi = (unsigned *)(so + hl + (N - p.hs));
@@ -355,22 +378,28 @@ __global__ __launch_bounds__(TPB) void pv_stretch_pass_b(PvStretchParams p)
     }
 }
 
-std::atomic<bool> g_lds_a[8][16], g_lds_b[8][16];
+std::atomic<bool> g_lds_a[2][8][16], g_lds_b[2][8][16];
+
+template <int LOG2N, bool SCHED>
+hipError_t launch_t(const PvStretchParams &p, hipStream_t st)
+{
+    using C = SC<LOG2N>;
+    hipError_t e = pv_set_dynamic_lds_once(g_lds_a[SCHED][LOG2N - 8], (const void *)pv_stretch_pass_a<LOG2N, SCHED>, (int)C::LDS_A);
+    if (e != hipSuccess) return e;
+    e = pv_set_dynamic_lds_once(g_lds_b[SCHED][LOG2N - 8], (const void *)pv_stretch_pass_b<LOG2N, SCHED>, (int)C::LDS_B);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)p.nchains, (unsigned)p.nch);
+    hipLaunchKernelGGL((pv_stretch_pass_a<LOG2N, SCHED>), grid, dim3(TPB), C::LDS_A, st, p);
+    const long scan_threads = (long)p.nch * C::H;
+    hipLaunchKernelGGL(pv_stretch_scan, dim3((unsigned)((scan_threads + TPB - 1) / TPB)), dim3(TPB), 0, st, p, C::N);
+    hipLaunchKernelGGL((pv_stretch_pass_b<LOG2N, SCHED>), grid, dim3(TPB), C::LDS_B, st, p);
+    return hipGetLastError();
+}
 
 template <int LOG2N>
 hipError_t launch_t(const PvStretchParams &p, hipStream_t st)
 {
-    using C = SC<LOG2N>;
-    hipError_t e = pv_set_dynamic_lds_once(g_lds_a[LOG2N - 8], (const void *)pv_stretch_pass_a<LOG2N>, (int)C::LDS_A);
-    if (e != hipSuccess) return e;
-    e = pv_set_dynamic_lds_once(g_lds_b[LOG2N - 8], (const void *)pv_stretch_pass_b<LOG2N>, (int)C::LDS_B);
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)p.nchains, (unsigned)p.nch);
-    hipLaunchKernelGGL(pv_stretch_pass_a<LOG2N>, grid, dim3(TPB), C::LDS_A, st, p);
-    const long scan_threads = (long)p.nch * C::H;
-    hipLaunchKernelGGL(pv_stretch_scan, dim3((unsigned)((scan_threads + TPB - 1) / TPB)), dim3(TPB), 0, st, p, C::N);
-    hipLaunchKernelGGL(pv_stretch_pass_b<LOG2N>, grid, dim3(TPB), C::LDS_B, st, p);
-    return hipGetLastError();
+    return p.pos ? launch_t<LOG2N, true>(p, st) : launch_t<LOG2N, false>(p, st);
 }
 
 }  // namespace

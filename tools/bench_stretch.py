@@ -3,7 +3,9 @@
 Same discipline as bench.py: HBM-resident input, `--warmup` untimed launches, then `--steps` launches bracketed by HIP events on the launch stream.
 frames/s counts channel-frames; `hbm_fraction` is the algorithmic traffic of a frame, (ha + hs) * 4 B, against 8 TB/s.  Two comparison lines time the
 pitch kernel on the same input: the headline form (pitchFactor 1.5), and the GPU part of the host speed path (pitch-shift-cli.js --speed 1.25: the input
-resampled to 0.8x on the host, then the pitch kernel at pitchFactor 1 / 1.25), which produces the same output duration as a 1.25x stretch.
+resampled to 0.8x on the host, then the pitch kernel at pitchFactor 1 / 1.25), which produces the same output duration as a 1.25x stretch.  The tempo
+line runs the mono 1024 shape through pv_tempo_process_device on a handle with floor 205, its schedule sweeping the analysis hop 205 -> 320 -> 205 (mean
+262.5, next to the fixed 256): the per-frame position table against the fixed hop.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576]
 """
@@ -11,6 +13,8 @@ import argparse
 import json
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,6 +50,24 @@ def stretch_line(torch, phaze_amd, N, ha, hs, nch, T, steps, warmup):
             "frames_per_s": frames / (ms * 1e-3), "hbm_fraction": frames * (ha + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def tempo_line(torch, phaze_amd, N, lo, hi, hs, T, steps, warmup):
+    period = 2 * (hi - lo)
+    tri = np.abs((np.arange(T) % period) - (hi - lo))                # hi - lo .. 0 .. hi - lo
+    hops = (hi - tri).astype(np.int32)
+    n = int(hops.astype(np.int64).sum())
+    x = (torch.rand((1, n), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, T * hs), device="cuda")
+    ts = phaze_amd.TimeStretch(N, lo, hs, max_channels=1)
+    stream = torch.cuda.Stream()
+    ts.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ts.process_hops_device(x.data_ptr(), y.data_ptr(), 1, T, hops, n, T * hs), steps, warmup)
+    ts.close()
+    return {"kernel": "pv_tempo", "fft": N, "analysis_hop_min": int(hops.min()), "analysis_hop_max": int(hops.max()), "analysis_hop_mean": n / T,
+            "synthesis_hop": hs, "channels": 1, "frames_per_channel": T, "ms_per_launch": round(ms, 4), "frames_per_s": T / (ms * 1e-3),
+            "hbm_fraction": T * (n / T + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -68,6 +90,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=1 << 20, help="frames per channel of the mono 1024 shape (the others keep its sample count)")
     ap.add_argument("--no-compare", action="store_true", help="skip the two pitch-kernel comparison lines")
+    ap.add_argument("--no-tempo", action="store_true", help="skip the variable-tempo line")
     args = ap.parse_args()
     import torch
     import phaze_amd
@@ -75,6 +98,8 @@ def main():
     shapes = [(1024, 256, 320, 1, T), (2048, 512, 640, 2, T // 2), (4096, 1024, 1280, 8, T // 8)]
     for N, ha, hs, nch, t in shapes:
         print(json.dumps(stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup)), flush=True)
+    if not args.no_tempo:
+        print(json.dumps(tempo_line(torch, phaze_amd, 1024, 205, 320, 320, T, args.steps, args.warmup)), flush=True)
     if not args.no_compare:
         print(json.dumps(pitch_line(torch, phaze_amd, "pitch headline, same input", 1024, 256, 1, T, 1.5, args.steps, args.warmup)), flush=True)
         # --speed 1.25: 0.8x as many input frames after the host resampler, pitch 1 / 1.25: the same output duration as the 1.25x stretch above

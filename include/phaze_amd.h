@@ -50,7 +50,8 @@ typedef struct pv_handle pv_handle;
  * 4 = round 5: PV_FLAG_FP64_FORWARD, pv_forward_stats;
  * 5 = round 6: PV_FLAG_TEST_FAIL_SECOND_PIECE (a test hook); no layout or semantic change of anything that existed;
  * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed.  Later, still 6 (additive: new symbols only, no
- *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device. */
+ *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device; linked channels,
+ *     pv_link_channels (an unlinked handle behaves as before). */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -254,7 +255,8 @@ PV_API int pv_debug_frame(pv_handle *h, int32_t ch, const float *block, float pi
  * Each frame consumes analysis_hop (ha) input samples and emits synthesis_hop (hs) output samples: the output lasts hs / ha times as long.
  * Phases are u32 fixed-point turns, so every carried quantity is an integer sum: any split of a stream into calls gives the same bits.
  * The output lags the input by N - hs samples.  N = 256 .. 8192 (outside: PV_ERR_FFT_SIZE / PV_ERR_UNSUPPORTED as pv_create), ha in 1..N,
- * hs in 1..N/2 (at least two overlapping output frames; each frame is scaled by hs / N).  See INTEGRATION.md "Time stretch". */
+ * hs in 1..N/2 (at least two overlapping output frames; each frame is scaled by hs / N).  See INTEGRATION.md "Time stretch".
+ * Each channel slot keeps its own phases unless pv_link_channels groups them (one phase track per group: the stereo image survives). */
 typedef struct pv_stretch_config {
     int32_t struct_size;     /* sizeof(pv_stretch_config) as the caller compiled it (PV_STRETCH_CONFIG_INIT sets it)          */
     int32_t fft_size;        /* N, power of two, 256 .. 8192                                                                      */
@@ -310,6 +312,17 @@ PV_API int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t 
 /* The same on DEVICE in / out pointers, asynchronous on the handle's stream. */
 PV_API int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes,
                                    const int32_t *hops, int64_t hop_stride, int64_t in_stride, int64_t out_stride);
+
+/* ---- linked channels on a time-stretch handle: one phase track per group ----------------------------------------------------------- */
+/* Slots [g*G, (g+1)*G) become group g (G = channels_per_group, 1 .. max_channels; 1 = every slot on its own, the default).  Per frame the group's
+ * channels are summed in slot order (f32), that mix runs the phase path of a mono handle (peaks, regions, analysis phase, phase advance), and every
+ * channel's bin k is rotated by the mix's angle for k: inter-channel phase and amplitude ratios are kept, and the sum of a group's outputs is the
+ * mono stretch of its mix up to rounding.  A frame whose mix has no peak (e.g. an exactly anti-phase pair, L = -R) is silent in every channel.
+ * Resets every slot as pv_stretch_reset does (which keeps the setting).  On a linked handle pv_stretch_process* and pv_tempo_process* reject, with
+ * PV_ERR_ARGUMENT before any device work and the state untouched, an nch that is not a multiple of G and, with hop_stride != 0, schedule rows that
+ * differ within a group (the message names the group and the first frame).  State: the group's phi / psi are read from slot g*G and every call
+ * writes them into every slot of the group (export any slot; import into slot g*G); hist / acc stay per slot.  See INTEGRATION.md "Linked channels". */
+PV_API int pv_link_channels(pv_stretch *h, int32_t channels_per_group);
 
 #ifdef __cplusplus
 }

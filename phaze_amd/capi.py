@@ -26,6 +26,7 @@ EXPORTS = [
     "pv_stretch_create", "pv_stretch_destroy", "pv_stretch_reset", "pv_stretch_last_error", "pv_stretch_process", "pv_stretch_process_device",
     "pv_stretch_set_stream", "pv_stretch_synchronize", "pv_stretch_export_state", "pv_stretch_import_state",
     "pv_tempo_process", "pv_tempo_process_device",
+    "pv_link_channels",
 ]
 
 
@@ -138,6 +139,7 @@ def load_library():
     ip = C.POINTER(C.c_int32)
     L.pv_tempo_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
     L.pv_tempo_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_link_channels.argtypes = [vp, C.c_int32]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -437,9 +439,10 @@ def tempo_hops(tempo, synthesis_hop, min_hop, max_hop, carry=0.0):
 class TimeStretch:
     """Phase-locked time stretch (pv_stretch_*): tempo change at constant pitch.  Each frame consumes `analysis_hop` input samples and emits
     `synthesis_hop` output samples, so the output lasts synthesis_hop / analysis_hop times as long; it lags the input by fft_size - synthesis_hop
-    samples.  State carries across calls: any split of a stream into calls gives the same bits."""
+    samples.  State carries across calls: any split of a stream into calls gives the same bits.  channels_per_group > 1 links consecutive channel
+    slots into groups with one phase track each (pv_link_channels, link_channels): the stereo image survives the stretch."""
 
-    def __init__(self, fft_size, analysis_hop, synthesis_hop, max_channels=1, max_frames=1, device_id=0):
+    def __init__(self, fft_size, analysis_hop, synthesis_hop, max_channels=1, max_frames=1, device_id=0, channels_per_group=1):
         self._L = load_library()
         self._h = C.c_void_p()
         cfg = make_stretch_config(fft_size, analysis_hop, synthesis_hop, max_channels, max_frames, device_id, 0)
@@ -452,6 +455,13 @@ class TimeStretch:
             raise PvError(rc, msg)
         self.fft_size, self.analysis_hop, self.synthesis_hop = fft_size, analysis_hop, synthesis_hop
         self.max_channels, self.max_frames = max_channels, max_frames
+        self.channels_per_group = 1
+        if channels_per_group != 1:
+            try:
+                self.link_channels(channels_per_group)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -469,7 +479,17 @@ class TimeStretch:
             raise PvError(rc, self._L.pv_stretch_last_error(self._h).decode())
 
     def reset(self):
+        """Zero every slot's state; the channel linking stays."""
         self._check(self._L.pv_stretch_reset(self._h))
+
+    def link_channels(self, channels_per_group):
+        """pv_link_channels: slots [g G, (g + 1) G) become one group with one phase track (G = 1: every slot on its own).  Resets every slot."""
+        self._check(self._L.pv_link_channels(self._h, int(channels_per_group)))
+        self.channels_per_group = int(channels_per_group)
+
+    def _check_groups(self, nch):
+        if nch % self.channels_per_group:
+            raise ValueError(f"{nch} channels are not a whole number of linked groups of {self.channels_per_group}")
 
     def process(self, x):
         """x: float32[nch, nframes * analysis_hop] (host) -> float32[nch, nframes * synthesis_hop] for channel slots 0 .. nch-1."""
@@ -480,6 +500,7 @@ class TimeStretch:
         nframes = n // self.analysis_hop
         if nframes * self.analysis_hop != n:
             raise ValueError("the input length must be a whole number of analysis hops")
+        self._check_groups(nch)
         y = np.empty((nch, nframes * self.synthesis_hop), np.float32)
         if nch and nframes:
             self._check(self._L.pv_stretch_process(self._h, _fp(x), _fp(y), nch, nframes, n, nframes * self.synthesis_hop))
@@ -487,6 +508,7 @@ class TimeStretch:
 
     def process_device(self, d_in, d_out, nch, nframes, in_stride, out_stride):
         """Raw device pointers (ints).  Asynchronous on the handle's stream."""
+        self._check_groups(nch)
         self._check(self._L.pv_stretch_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, in_stride, out_stride))
 
     @staticmethod
@@ -515,6 +537,7 @@ class TimeStretch:
                 raise ValueError(f"{h.shape[0]} schedule rows for {nch} channels")
             if nframes and int(h.astype(np.int64).sum(axis=1).max()) > n:
                 raise ValueError("the input is shorter than a row of the schedule consumes")
+        self._check_groups(nch)
         y = np.empty((nch, nframes * self.synthesis_hop), np.float32)
         if nch and nframes:
             self._check(self._L.pv_tempo_process(self._h, _fp(x), _fp(y), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)), stride, n,
@@ -529,6 +552,7 @@ class TimeStretch:
             raise ValueError(f"{h.size} hops for {nframes} frames")
         if h.ndim == 2 and h.shape[0] < nch:
             raise ValueError(f"{h.shape[0]} schedule rows for {nch} channels")
+        self._check_groups(nch)
         self._check(self._L.pv_tempo_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)),
                                                     stride, in_stride, out_stride))
 

@@ -33,3 +33,8 @@ size_t pv_stretch_lds_bytes(int log2n, bool pass_b);
 int pv_stretch_threads();
 // pass A + scan + pass B on `st`; the caller then copies state_out back into its state
 hipError_t pv_launch_stretch(int log2n, const PvStretchParams &p, hipStream_t st);
+// the scan alone (pv_stretch_scan over p.nch slots of p.state_stride floats): linked channels run it once per group
+hipError_t pv_launch_stretch_scan(int log2n, const PvStretchParams &p, hipStream_t st);
+// linked channels (pv_link_kernels.hip), G >= 2 consecutive slots per group, p.nch a multiple of G: pass A per (chain, group), the scan per group,
+// pass B per (chain, channel); p.sums holds [nch / G][nchains][2][H]
+hipError_t pv_launch_link(int log2n, const PvStretchParams &p, int G, hipStream_t st);

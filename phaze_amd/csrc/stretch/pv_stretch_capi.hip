@@ -3,6 +3,7 @@
 // Owns one time-stretch handle's device state -- per channel slot hist[N - ha] | acc[N - hs] | phi[H] | psi[H] (pv_stretch.h) -- and turns calls
 // into pass A + scan + pass B launches (pv_stretch_kernels.hip).  No CPU compute path: without a HIP device pv_stretch_create fails with PV_ERR_DEVICE.
 // pv_tempo_process / pv_tempo_process_device (variable tempo) turn a host schedule of per-frame hops into the kernels' position table.
+// pv_link_channels groups consecutive slots: a linked handle runs pv_link_kernels.hip (one phase track per group) in place of the unlinked passes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -38,6 +39,7 @@ struct pv_stretch {
     size_t pos_cap, hpos_cap;    // (in int64 words)
     hipEvent_t pos_done;         // recorded behind the last upload: h_pos may be rewritten once it has completed
     bool pos_pending;
+    int group;                   // channels per linked group (pv_link_channels), 1: unlinked
     char err[256];
 };
 
@@ -90,14 +92,14 @@ int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, lo
     memset(&p, 0, sizeof p);
     p.in = d_in; p.out = d_out; p.in_stride = in_stride; p.out_stride = out_stride;
     p.nframes = nframes; p.nch = nch; p.ha = h->ha; p.hs = h->hs;
-    p.F = pick_chain(h, nch, nframes);
+    p.F = pick_chain(h, nch / h->group, nframes);                      // linked: chains enough to fill the chip with pass A's nch / G workgroups
     p.nchains = (nframes + p.F - 1) / p.F;
     p.halo = h->halo;
     p.ola_scale = (float)((double)h->hs / (double)h->N);
     p.state_in = h->d_state; p.state_out = h->d_state_out; p.state_stride = h->stride;
     p.tw64 = h->d_tw64; p.tw32 = h->d_tw32; p.hann = h->d_hann;
     p.pos = d_pos; p.pos_stride = pos_stride;
-    const size_t words = (size_t)nch * (size_t)p.nchains * 2 * (size_t)h->H;
+    const size_t words = (size_t)(nch / h->group) * (size_t)p.nchains * 2 * (size_t)h->H;
     if (words > h->sums_cap) {
         SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still use the old buffer
         if (h->d_sums) (void)hipFree(h->d_sums);
@@ -106,7 +108,7 @@ int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, lo
         h->sums_cap = words;
     }
     p.sums = h->d_sums;
-    SCHK(h, pv_launch_stretch(h->log2n, p, h->stream));
+    SCHK(h, h->group > 1 ? pv_launch_link(h->log2n, p, h->group, h->stream) : pv_launch_stretch(h->log2n, p, h->stream));
     SCHK(h, hipMemcpyAsync(h->d_state, h->d_state_out, sizeof(float) * (size_t)nch * (size_t)h->stride, hipMemcpyDeviceToDevice, h->stream));
     return PV_OK;
 }
@@ -116,6 +118,11 @@ int check_call(pv_stretch *h, const void *in, const void *out, int32_t nch, int3
     if (!in || !out) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: null buffer");
     if (nch < 0 || nframes < 0) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: negative channel or frame count");
     if (nch > h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_process: more channels than max_channels");
+    if (nch % h->group != 0) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "pv_stretch_process: %d channels are not a whole number of linked groups of %d", nch, h->group);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
     if (nch > 1 && (in_stride < (int64_t)nframes * h->ha || out_stride < (int64_t)nframes * h->hs))
         return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: channel strides shorter than nframes * hop");
     return PV_OK;
@@ -131,6 +138,10 @@ int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, 
     if (!in || !out) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
     if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
     if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
+    if (nch % h->group != 0) {
+        snprintf(msg, sizeof msg, "%s: %d channels are not a whole number of linked groups of %d", fn, nch, h->group);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
     if (nframes > 0 && !hops) { snprintf(msg, sizeof msg, "%s: null hops", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
     if (hop_stride != 0 && hop_stride < nframes) {
         snprintf(msg, sizeof msg, "%s: hop_stride %lld is neither 0 (one row for every channel) nor >= nframes %d", fn, (long long)hop_stride, nframes);
@@ -151,6 +162,17 @@ int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, 
         }
         tot[(size_t)r] = t;
         if (t > most) most = t;
+    }
+    // linked channels share their group's phase track and so its schedule: every row of a group must equal the group's first
+    for (int r = 0; r < nrows && nrows > 1 && nframes > 0; r++) {
+        if (r % h->group == 0) continue;
+        const int32_t *row = hops + (size_t)r * (size_t)hop_stride, *first = hops + (size_t)(r - r % h->group) * (size_t)hop_stride;
+        for (int m = 0; m < nframes; m++)
+            if (row[m] != first[m]) {
+                snprintf(msg, sizeof msg, "%s: schedule rows differ within linked group %d (channels %d .. %d): channel %d, frame %d", fn, r / h->group,
+                         r - r % h->group, r - r % h->group + h->group - 1, r, m);
+                return sfail(h, PV_ERR_ARGUMENT, msg);
+            }
     }
     if (nch > 1 && (in_stride < most || out_stride < (int64_t)nframes * h->hs)) {
         snprintf(msg, sizeof msg, "%s: channel strides shorter than the largest row's input (%lld) or nframes * synthesis_hop (%lld)", fn, most,
@@ -227,6 +249,7 @@ int pv_stretch_create(const pv_stretch_config *cfg, pv_stretch **out)
     h->magic = kStretchMagic;
     h->N = N; h->log2n = log2n; h->ha = ha; h->hs = hs; h->H = N / 2 + 1; h->halo = (N - 1) / hs;
     h->max_channels = maxch; h->max_frames = maxfr; h->device = cfg->device_id;
+    h->group = 1;
     h->stride = pv_stretch_state_stride(N, ha, hs);
 
 #define CCHK(call)                                                         \
@@ -299,6 +322,20 @@ int pv_stretch_reset(pv_stretch *h)
     SCHK(h, hipSetDevice(h->device));
     SCHK(h, hipMemsetAsync(h->d_state, 0, sizeof(float) * (size_t)h->max_channels * (size_t)h->stride, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
+    return PV_OK;
+}
+
+int pv_link_channels(pv_stretch *h, int32_t channels_per_group)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    if (channels_per_group < 1 || channels_per_group > h->max_channels) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "pv_link_channels: channels_per_group %d outside [1, max_channels %d]", (int)channels_per_group, h->max_channels);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
+    const int rc = pv_stretch_reset(h);                                // per-channel and per-group phases mean different things
+    if (rc != PV_OK) return rc;
+    h->group = channels_per_group;
     return PV_OK;
 }
 

@@ -5,7 +5,8 @@ frames/s counts channel-frames; `hbm_fraction` is the algorithmic traffic of a f
 pitch kernel on the same input: the headline form (pitchFactor 1.5), and the GPU part of the host speed path (pitch-shift-cli.js --speed 1.25: the input
 resampled to 0.8x on the host, then the pitch kernel at pitchFactor 1 / 1.25), which produces the same output duration as a 1.25x stretch.  The tempo
 line runs the mono 1024 shape through pv_tempo_process_device on a handle with floor 205, its schedule sweeping the analysis hop 205 -> 320 -> 205 (mean
-262.5, next to the fixed 256): the per-frame position table against the fixed hop.
+262.5, next to the fixed 256): the per-frame position table against the fixed hop.  The linked lines (pv_link_channels) run the stereo 2048 shape
+with G = 2, the 8-channel 4096 shape with G = 8 and as four stereo pairs (G = 2), each with its ratio to the unlinked line of the same shape.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576]
 """
@@ -36,17 +37,17 @@ def _time(torch, stream, fn, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
-def stretch_line(torch, phaze_amd, N, ha, hs, nch, T, steps, warmup):
+def stretch_line(torch, phaze_amd, N, ha, hs, nch, T, steps, warmup, G=1):
     x = (torch.rand((nch, T * ha), device="cuda") - 0.5).contiguous()
     y = torch.empty((nch, T * hs), device="cuda")
-    ts = phaze_amd.TimeStretch(N, ha, hs, max_channels=nch)
+    ts = phaze_amd.TimeStretch(N, ha, hs, max_channels=nch, channels_per_group=G)
     stream = torch.cuda.Stream()
     ts.set_stream(stream.cuda_stream)
     torch.cuda.synchronize()
     ms = _time(torch, stream, lambda: ts.process_device(x.data_ptr(), y.data_ptr(), nch, T, T * ha, T * hs), steps, warmup)
     ts.close()
     frames = nch * T
-    return {"kernel": "pv_stretch", "fft": N, "analysis_hop": ha, "synthesis_hop": hs, "channels": nch, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
+    return {"kernel": "pv_stretch" if G == 1 else "pv_link", "channels_per_group": G, "fft": N, "analysis_hop": ha, "synthesis_hop": hs, "channels": nch, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
             "frames_per_s": frames / (ms * 1e-3), "hbm_fraction": frames * (ha + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
@@ -91,13 +92,22 @@ def main():
     ap.add_argument("--frames", type=int, default=1 << 20, help="frames per channel of the mono 1024 shape (the others keep its sample count)")
     ap.add_argument("--no-compare", action="store_true", help="skip the two pitch-kernel comparison lines")
     ap.add_argument("--no-tempo", action="store_true", help="skip the variable-tempo line")
+    ap.add_argument("--no-link", action="store_true", help="skip the linked-channel lines")
     args = ap.parse_args()
     import torch
     import phaze_amd
     T = args.frames
     shapes = [(1024, 256, 320, 1, T), (2048, 512, 640, 2, T // 2), (4096, 1024, 1280, 8, T // 8)]
+    unlinked = {}
     for N, ha, hs, nch, t in shapes:
-        print(json.dumps(stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup)), flush=True)
+        r = stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup)
+        unlinked[(N, nch)] = r["frames_per_s"]
+        print(json.dumps(r), flush=True)
+    if not args.no_link:
+        for N, ha, hs, nch, t, G in [(2048, 512, 640, 2, T // 2, 2), (4096, 1024, 1280, 8, T // 8, 8), (4096, 1024, 1280, 8, T // 8, 2)]:
+            r = stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup, G)
+            r["ratio_to_unlinked"] = round(r["frames_per_s"] / unlinked[(N, nch)], 4)
+            print(json.dumps(r), flush=True)
     if not args.no_tempo:
         print(json.dumps(tempo_line(torch, phaze_amd, 1024, 205, 320, 320, T, args.steps, args.warmup)), flush=True)
     if not args.no_compare:

@@ -51,7 +51,8 @@ typedef struct pv_handle pv_handle;
  * 5 = round 6: PV_FLAG_TEST_FAIL_SECOND_PIECE (a test hook); no layout or semantic change of anything that existed;
  * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed.  Later, still 6 (additive: new symbols only, no
  *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device; linked channels,
- *     pv_link_channels (an unlinked handle behaves as before). */
+ *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
+ *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged). */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -323,6 +324,59 @@ PV_API int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_ou
  * differ within a group (the message names the group and the first frame).  State: the group's phi / psi are read from slot g*G and every call
  * writes them into every slot of the group (export any slot; import into slot g*G); hist / acc stay per slot.  See INTEGRATION.md "Linked channels". */
 PV_API int pv_link_channels(pv_stretch *h, int32_t channels_per_group);
+
+/* ---- phase resets on a time-stretch handle: transients pass unstretched ------------------------------------------------------------ */
+/* pv_tempo_process plus a HOST row of per-frame flags, resets[c * reset_stride + m] in {0, 1} (reset_stride == 0: every channel uses row 0; else
+ * >= nframes, one row per channel slot): a flagged frame sets its synthesis phase to its analysis phase in every bin, psi := q, instead of advancing
+ * it, so its rotation angle is zero and its output is Hann * IDFT(X) * hs / N.  Every following frame with hop == synthesis_hop keeps psi == q exactly
+ * (integer arithmetic), so a reset followed by a run of unit-tempo frames reproduces the input sample for sample under the overlap-add envelope:
+ * the classical way to carry an attack through a stretch.  A reset alone, without the hold, gains nothing (see INTEGRATION.md "Transients").
+ * hops == NULL: every hop equals analysis_hop (the fixed-hop call with resets).  resets == NULL: no reset, the bits of pv_tempo_process.  Any split
+ * of a schedule into calls gives the same bits, as before; the two rows are HOST arrays read before the call returns.
+ * Rejected as pv_tempo_process rejects, and also (PV_ERR_ARGUMENT, before any device work, state untouched): a flag other than 0 / 1, a reset_stride
+ * that is neither 0 nor >= nframes, and on a linked handle reset rows that differ within a group (a group has one phase track: psi_g := q of the mix).
+ * Host pointers, synchronous, staged in pieces as pv_tempo_process. */
+PV_API int pv_transient_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops,
+                                int64_t hop_stride, const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride);
+/* The same on DEVICE in / out pointers, asynchronous on the handle's stream. */
+PV_API int pv_transient_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes,
+                                       const int32_t *hops, int64_t hop_stride, const uint8_t *resets, int64_t reset_stride,
+                                       int64_t in_stride, int64_t out_stride);
+/* Onset strength of a buffer, with the stretch's own front end (Hann, fp64 forward, f32 |X|^2; a linked group analyses its f32 mix).  Frames at the
+ * handle's analysis_hop: frame m's window is the N samples that end at (m + 1) * analysis_hop, samples before the buffer are zeros, frame -1 is all
+ * zeros.  counts[g * count_stride + m] = the number of bins k in [1, N/2) with mag_m[k] > 4 * mag_{m-1}[k] and mag_m[k] > 2^-20 * max_k mag_m, for
+ * group g (slot g when unlinked) of in[c * in_stride .. + nframes * analysis_hop).  A pure function of the buffer: it neither reads nor writes the
+ * handle's carried state.  A stream analysed in pieces overlaps them by N + analysis_hop samples and drops the frames that saw the padding.
+ * Thresholds and peak picking stay with the caller (pv_onsets_from_strength).  Host pointers, synchronous. */
+PV_API int pv_onset_strength(pv_stretch *h, const float *in, int32_t nch, int32_t nframes, int64_t in_stride, int32_t *counts,
+                             int64_t count_stride);
+/* The same on DEVICE in / counts pointers, asynchronous on the handle's stream. */
+PV_API int pv_onset_strength_device(pv_stretch *h, const float *d_in, int32_t nch, int32_t nframes, int64_t in_stride,
+                                    int32_t *d_counts, int64_t count_stride);
+/* Pure host code, no handle and no device.  Frame m is an onset when counts[m] >= tau * (N/2 - 1) and counts[m - 1] is below it (counts[-1] = 0);
+ * its position is m * analysis_hop input samples.  tau > 0; 0.4 separates the measured classes (stationary noise <= 0.20, onsets >= 0.66).
+ * Two-call sizing, here and in pv_transient_plan: the return value is the number of entries the result has; at most `capacity` of them are written
+ * (capacity 0 with NULL arrays only counts).  Errors return -PV_ERR_ARGUMENT. */
+PV_API int64_t pv_onsets_from_strength(const int32_t *counts, int64_t nframes, int32_t fft_size, int32_t analysis_hop, double tau,
+                                       int64_t *onsets, int64_t capacity);
+/* The hop row and reset row of pv_transient_process for sorted onset positions (input samples) in an input of input_len samples: nominal tempo
+ * synthesis_hop / nominal_hop, with every onset carried through a hold.  Frame by frame, S the input consumed so far: a frame is HELD when, after
+ * its hop, the part [lead, N - lead) of its window meets an attack, taken to last from its onset position to `release` samples behind it (the hop
+ * tried is nominal_hop, or synthesis_hop when the previous frame was held);
+ * a held frame has hop synthesis_hop, and the first frame of a run of held frames has its reset flag set.  Other frames have hop
+ * nominal_hop - clamp(debt, -kappa, kappa) clamped to [floor_hop, N], debt = S - frames * nominal_hop, kappa = max(1, nominal_hop / 8): the total
+ * length returns to nominal after each hold.  Stops when the next hop would pass input_len.  floor_hop is the handle's analysis_hop; lead in
+ * 0 .. N/2, negative = the default N/8 (N/4 holds too little: measured).  release in 0 .. N, negative = the default N/2; 0 holds only while the
+ * onset position itself is inside [lead, N - lead), which ends the hold while the attack's decay is still in the window: the frames after the hold
+ * then place that decay late (measured: the attack's energy spread doubles at synthesis_hop = 3N/8).  A hold must in any case exceed N /
+ * synthesis_hop frames, release > 2 * lead, for any output to come from held frames alone.  -PV_ERR_ARGUMENT: synthesis_hop < floor_hop (a hold needs hop ==
+ * synthesis_hop to be legal: create a speed-up handle with analysis_hop <= synthesis_hop), nominal_hop outside [floor_hop, N], unsorted onsets. */
+PV_API int64_t pv_transient_plan(const int64_t *onsets, int64_t nonsets, int64_t input_len, int32_t fft_size, int32_t nominal_hop,
+                                 int32_t floor_hop, int32_t synthesis_hop, int32_t lead, int32_t release, int32_t *hops, uint8_t *resets,
+                                 int64_t capacity);
+/* TEST HOOK, never needed in production: how this chip cuts a call of nch channels and nframes frames into chains (frames per chain; halo =
+ * (N - 1) / synthesis_hop earlier frames each chain recomputes), so that tests can put resets on chain and halo boundaries. */
+PV_API int pv_transient_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32_t *frames_per_chain, int32_t *halo);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,8 @@ EXPORTS = [
     "pv_stretch_set_stream", "pv_stretch_synchronize", "pv_stretch_export_state", "pv_stretch_import_state",
     "pv_tempo_process", "pv_tempo_process_device",
     "pv_link_channels",
+    "pv_transient_process", "pv_transient_process_device", "pv_onset_strength", "pv_onset_strength_device", "pv_transient_plan",
+    "pv_onsets_from_strength", "pv_transient_chain_layout",
 ]
 
 
@@ -140,9 +142,18 @@ def load_library():
     L.pv_tempo_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
     L.pv_tempo_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, C.c_int64, C.c_int64, C.c_int64]
     L.pv_link_channels.argtypes = [vp, C.c_int32]
+    bp, lp = C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
+    L.pv_transient_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, ip, C.c_int64, bp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_transient_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, C.c_int64, bp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_onset_strength.argtypes = [vp, fp, C.c_int32, C.c_int32, C.c_int64, ip, C.c_int64]
+    L.pv_onset_strength_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64]
+    L.pv_onsets_from_strength.argtypes = [ip, C.c_int64, C.c_int32, C.c_int32, C.c_double, lp, C.c_int64]
+    L.pv_transient_plan.argtypes = [lp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, bp, C.c_int64]
+    L.pv_transient_chain_layout.argtypes = [vp, C.c_int32, C.c_int32, ip, ip]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
+    L.pv_onsets_from_strength.restype = L.pv_transient_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -436,6 +447,44 @@ def tempo_hops(tempo, synthesis_hop, min_hop, max_hop, carry=0.0):
     return hops, e
 
 
+def onsets_from_strength(counts, fft_size, analysis_hop, tau=0.4):
+    """pv_onsets_from_strength: int64 onset positions (input samples) from one row of onset counts (TimeStretch.onset_strength).  Frame m is an onset
+    when counts[m] >= tau (fft_size / 2 - 1) and counts[m - 1] is below it; its position is m * analysis_hop."""
+    L = load_library()
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    if c.ndim != 1:
+        raise ValueError("counts must be one row, int[nframes]")
+    ip, lp = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    n = L.pv_onsets_from_strength(c.ctypes.data_as(ip), c.size, fft_size, analysis_hop, float(tau), None, 0)
+    if n < 0:
+        raise ValueError("onsets_from_strength: bad argument (tau must be > 0, fft_size >= 4, analysis_hop >= 1)")
+    out = np.zeros(n, np.int64)
+    if n:
+        L.pv_onsets_from_strength(c.ctypes.data_as(ip), c.size, fft_size, analysis_hop, float(tau), out.ctypes.data_as(lp), n)
+    return out
+
+
+def transient_plan(onsets, input_len, fft_size, nominal_hop, floor_hop, synthesis_hop, lead=None, release=None):
+    """pv_transient_plan: (hops int32[T], resets uint8[T]) for TimeStretch.process_hops(x[:, :hops.sum()], hops, resets).  onsets: sorted positions in
+    input samples; nominal_hop: the hop outside holds (tempo synthesis_hop / nominal_hop); floor_hop: the handle's analysis_hop; lead: 0 .. fft_size/2,
+    default fft_size / 8; release: how many samples behind its position an attack is taken to last, 0 .. fft_size, default fft_size / 2 (a frame is
+    held while [lead, N - lead) of its window meets [onset, onset + release]).  Raises ValueError when synthesis_hop < floor_hop (a hold runs at hop == synthesis_hop) or an argument is out of range."""
+    L = load_library()
+    o = np.ascontiguousarray(onsets, dtype=np.int64).ravel()
+    ip, lp, bp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    args = (o.ctypes.data_as(lp), o.size, int(input_len), fft_size, nominal_hop, floor_hop, synthesis_hop, -1 if lead is None else int(lead),
+            -1 if release is None else int(release))
+    if (lead is not None and lead < 0) or (release is not None and release < 0):
+        raise ValueError("lead must be within 0 .. fft_size / 2 and release within 0 .. fft_size")
+    n = L.pv_transient_plan(*args, None, None, 0)
+    if n < 0:
+        raise ValueError("transient_plan: bad argument (synthesis_hop >= floor_hop, floor_hop <= nominal_hop <= fft_size, lead <= fft_size / 2, release <= fft_size, sorted onsets)")
+    hops, resets = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    if n:
+        L.pv_transient_plan(*args, hops.ctypes.data_as(ip), resets.ctypes.data_as(bp), n)
+    return hops, resets
+
+
 class TimeStretch:
     """Phase-locked time stretch (pv_stretch_*): tempo change at constant pitch.  Each frame consumes `analysis_hop` input samples and emits
     `synthesis_hop` output samples, so the output lasts synthesis_hop / analysis_hop times as long; it lags the input by fft_size - synthesis_hop
@@ -521,14 +570,30 @@ class TimeStretch:
             raise ValueError("hops must be int[nframes] or int[nch, nframes]")
         return hops, hops.shape[1], hops.shape[1]
 
-    def process_hops(self, x, hops):
+    @staticmethod
+    def _reset_rows(resets, nframes):
+        """(uint8 array, reset_stride): a 1-D row of nframes flags is shared by every channel, a 2-D one [nch, >= nframes] holds a row per channel."""
+        r = np.ascontiguousarray(resets, dtype=np.uint8)
+        if r.ndim == 1 and r.size == nframes:
+            return r, 0
+        if r.ndim == 2 and r.shape[1] >= nframes:
+            return r, r.shape[1]
+        raise ValueError(f"resets must be [nframes] or [nch, >= nframes] with nframes = {nframes}")
+
+    def process_hops(self, x, hops, resets=None):
         """Variable tempo (pv_tempo_process): frame m of channel c consumes hops[m] (1-D) or hops[c, m] (2-D) input samples, each in
         [analysis_hop, fft_size], and emits synthesis_hop samples.  x: float32[nch, n] (host), n == hops.sum() for a 1-D schedule, n >= the largest
-        row sum for a 2-D one (each row reads its own prefix) -> float32[nch, nframes * synthesis_hop]."""
+        row sum for a 2-D one (each row reads its own prefix) -> float32[nch, nframes * synthesis_hop].
+        resets (pv_transient_process): 0 / 1 per frame, [nframes] or [nch, nframes]; a flagged frame sets psi := q (its output is the windowed input
+        frame), and the frames after it at hop == synthesis_hop stay the input sample for sample.  hops=None: every hop is analysis_hop."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim == 1:
             x = x[None, :]
         nch, n = x.shape
+        if hops is None:
+            if resets is None:
+                return self.process(x)
+            hops = np.full(n // self.analysis_hop, self.analysis_hop, np.int32)
         h, nframes, stride = self._hop_rows(hops)
         if h.ndim == 1 and int(h.astype(np.int64).sum()) != n:
             raise ValueError(f"the input holds {n} samples per channel, the schedule consumes {int(h.astype(np.int64).sum())}")
@@ -539,12 +604,18 @@ class TimeStretch:
                 raise ValueError("the input is shorter than a row of the schedule consumes")
         self._check_groups(nch)
         y = np.empty((nch, nframes * self.synthesis_hop), np.float32)
-        if nch and nframes:
+        if nch and nframes and resets is None:
             self._check(self._L.pv_tempo_process(self._h, _fp(x), _fp(y), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)), stride, n,
                                                  nframes * self.synthesis_hop))
+        elif nch and nframes:
+            r, rstride = self._reset_rows(resets, nframes)
+            if r.ndim == 2 and r.shape[0] != nch:
+                raise ValueError(f"{r.shape[0]} reset rows for {nch} channels")
+            self._check(self._L.pv_transient_process(self._h, _fp(x), _fp(y), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)), stride,
+                                                     r.ctypes.data_as(C.POINTER(C.c_uint8)), rstride, n, nframes * self.synthesis_hop))
         return y
 
-    def process_hops_device(self, d_in, d_out, nch, nframes, hops, in_stride, out_stride):
+    def process_hops_device(self, d_in, d_out, nch, nframes, hops, in_stride, out_stride, resets=None):
         """pv_tempo_process_device on raw device pointers (ints), asynchronous on the handle's stream.  hops: host int[nframes] (shared) or int[nch, >= nframes];
         the library has read it when this returns."""
         h, _, stride = self._hop_rows(hops)
@@ -553,8 +624,57 @@ class TimeStretch:
         if h.ndim == 2 and h.shape[0] < nch:
             raise ValueError(f"{h.shape[0]} schedule rows for {nch} channels")
         self._check_groups(nch)
+        if resets is not None:
+            r, rstride = self._reset_rows(resets, nframes)
+            if r.ndim == 2 and r.shape[0] < nch:
+                raise ValueError(f"{r.shape[0]} reset rows for {nch} channels")
+            self._check(self._L.pv_transient_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            stride, r.ctypes.data_as(C.POINTER(C.c_uint8)), rstride, in_stride, out_stride))
+            return
         self._check(self._L.pv_tempo_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, h.ctypes.data_as(C.POINTER(C.c_int32)),
                                                     stride, in_stride, out_stride))
+
+    def onset_strength(self, x):
+        """pv_onset_strength: x float32[nch, n] (host) -> int32[nch / channels_per_group, n // analysis_hop], per group and frame the number of bins
+        whose power rose more than fourfold over the previous frame and lies above 2^-20 of the frame's largest.  Frame m's window ends at
+        (m + 1) analysis_hop; zeros before x.  Stateless: the handle's carried state is neither read nor written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        self._check_groups(nch)
+        nframes = n // self.analysis_hop
+        counts = np.zeros((nch // self.channels_per_group, nframes), np.int32)
+        if nch and nframes:
+            self._check(self._L.pv_onset_strength(self._h, _fp(x), nch, nframes, n, counts.ctypes.data_as(C.POINTER(C.c_int32)), nframes))
+        return counts
+
+    def onset_strength_device(self, d_in, nch, nframes, in_stride, d_counts, count_stride):
+        """pv_onset_strength_device on raw device pointers (ints), asynchronous on the handle's stream."""
+        self._check_groups(nch)
+        self._check(self._L.pv_onset_strength_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, C.c_void_p(d_counts), count_stride))
+
+    def chain_layout(self, nch, nframes):
+        """(frames per chain, halo) of a call of nch channels and nframes frames on this chip (pv_transient_chain_layout, a test hook)."""
+        F, halo = C.c_int32(), C.c_int32()
+        self._check(self._L.pv_transient_chain_layout(self._h, nch, nframes, C.byref(F), C.byref(halo)))
+        return F.value, halo.value
+
+    def process_transients(self, x, tau=0.4, lead=None, hop=None, release=None):
+        """Offline stretch that carries attacks through unstretched: onset_strength -> onsets_from_strength(tau) -> transient_plan(lead, release) ->
+        process_hops(hops, resets).  x: float32[nch, n] (host).  hop: the nominal analysis hop outside holds (tempo synthesis_hop / hop), default
+        analysis_hop; for a speed-up create the handle with analysis_hop <= synthesis_hop and pass the nominal hop here.  Every channel follows ONE
+        schedule, planned from the onsets of all groups together, so channels stay aligned with each other.  Returns (y float32[nch, T *
+        synthesis_hop], hops, resets); the schedule consumes x[:, :hops.sum()]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        hop = self.analysis_hop if hop is None else int(hop)
+        counts = self.onset_strength(x)
+        onsets = np.unique(np.concatenate([onsets_from_strength(row, self.fft_size, self.analysis_hop, tau) for row in counts] + [np.zeros(0, np.int64)]))
+        hops, resets = transient_plan(onsets, x.shape[1], self.fft_size, hop, self.analysis_hop, self.synthesis_hop, lead, release)
+        y = self.process_hops(x[:, :int(hops.astype(np.int64).sum())], hops, resets)
+        return y, hops, resets
 
     def set_stream(self, hip_stream):
         self._check(self._L.pv_stretch_set_stream(self._h, C.c_void_p(hip_stream)))

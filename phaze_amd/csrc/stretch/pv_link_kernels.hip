@@ -24,33 +24,6 @@
 
 namespace {
 
-// Sample s of the mix of the G channels starting at a group's first slot: the carried hist (slot stride hist_stride) ++ the input (channel stride
-// in_stride).  One f32 rounding per add, in slot order.  The loads go out MIX_BATCH at a time before their adds: a load-add chain would wait one
-// memory latency per channel.
-constexpr int MIX_BATCH = 4;
-
-struct MixSrc {
-    const float *hist;
-    const float *in;
-    long hl, hist_stride, in_stride;
-    int G;
-    __device__ __forceinline__ float at(long s) const
-    {
-        const float *x = s < hl ? hist + s : in + (s - hl);
-        const long stride = s < hl ? hist_stride : in_stride;
-        float u = 0.0f;
-        for (int i0 = 0; i0 < G; i0 += MIX_BATCH) {
-            float v[MIX_BATCH];
-#pragma unroll
-            for (int i = 0; i < MIX_BATCH; i++) v[i] = i0 + i < G ? x[(i0 + i) * stride] : 0.0f;
-#pragma unroll
-            for (int i = 0; i < MIX_BATCH; i++)
-                if (i0 + i < G) u = i0 + i == 0 ? v[0] : __fadd_rn(u, v[i]);
-        }
-        return u;
-    }
-};
-
 template <int LOG2N, bool SCHED>
 __global__ __launch_bounds__(TPB) void pv_link_pass_a(PvStretchParams p, int G)
 {

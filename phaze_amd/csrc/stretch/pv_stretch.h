@@ -38,3 +38,11 @@ hipError_t pv_launch_stretch_scan(int log2n, const PvStretchParams &p, hipStream
 // linked channels (pv_link_kernels.hip), G >= 2 consecutive slots per group, p.nch a multiple of G: pass A per (chain, group), the scan per group,
 // pass B per (chain, channel); p.sums holds [nch / G][nchains][2][H]
 hipError_t pv_launch_link(int log2n, const PvStretchParams &p, int G, hipStream_t st);
+// phase resets (pv_transient_kernels.hip): the schedule passes with psi := q at flagged frames.  p.pos must be set; rst holds int32 prefix counts of the
+// flags, [rows][nframes + 1] (R[0] = 0, R[m + 1] - R[m] = frame m's flag), row of slot c at rst + c * rst_stride (0: one row for every slot).  G = 1:
+// unlinked, G >= 2: linked groups (the row of slot g G); p.sums holds [nch / G][nchains][2][H]
+hipError_t pv_launch_stretch_reset(int log2n, const PvStretchParams &p, int G, const int *rst, long rst_stride, hipStream_t st);
+// onset strength (pv_transient_kernels.hip): counts[g * count_stride + m] for the nch / G groups of `in` (channel c at in + c * in_stride, nframes * ha
+// samples), one workgroup per (chain of F frames, group); stateless
+hipError_t pv_launch_onset_strength(int log2n, const float *in, long in_stride, int nch, int G, int nframes, int ha, int F, const double2 *tw64,
+                                    const float *hann, int *counts, long count_stride, hipStream_t st);

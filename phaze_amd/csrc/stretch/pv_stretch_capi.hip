@@ -4,6 +4,8 @@
 // into pass A + scan + pass B launches (pv_stretch_kernels.hip).  No CPU compute path: without a HIP device pv_stretch_create fails with PV_ERR_DEVICE.
 // pv_tempo_process / pv_tempo_process_device (variable tempo) turn a host schedule of per-frame hops into the kernels' position table.
 // pv_link_channels groups consecutive slots: a linked handle runs pv_link_kernels.hip (one phase track per group) in place of the unlinked passes.
+// pv_transient_process / pv_transient_process_device add a host row of per-frame reset flags (pv_transient_kernels.hip), uploaded as prefix counts behind
+// the position table; pv_onset_strength runs the stateless detection kernel of the same file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -39,6 +41,10 @@ struct pv_stretch {
     size_t pos_cap, hpos_cap;    // (in int64 words)
     hipEvent_t pos_done;         // recorded behind the last upload: h_pos may be rewritten once it has completed
     bool pos_pending;
+    int *d_rst;                  // phase resets: the prefix counts of the last upload, inside d_pos behind the position table
+    float *d_onset_in;           // pv_onset_strength on host pointers: the whole buffer and its counts, grown on demand
+    int *d_onset_counts;
+    size_t onset_in_cap, onset_counts_cap;   // (in words)
     int group;                   // channels per linked group (pv_link_channels), 1: unlinked
     char err[256];
 };
@@ -84,9 +90,9 @@ int pick_chain(const pv_stretch *h, int nch, int nframes)
 }
 
 // One launch over channel slots [0, nch): device pointers, asynchronous on h->stream.  d_pos: the position table of a tempo call (pv_stretch.h), or
-// nullptr for the fixed hop.
+// nullptr for the fixed hop.  d_rst: the reset prefix counts of a transient call (needs d_pos), or nullptr.
 int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, long in_stride, long out_stride, const long long *d_pos = nullptr,
-        long pos_stride = 0)
+        long pos_stride = 0, const int *d_rst = nullptr, long rst_stride = 0)
 {
     PvStretchParams p;
     memset(&p, 0, sizeof p);
@@ -108,7 +114,8 @@ int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, lo
         h->sums_cap = words;
     }
     p.sums = h->d_sums;
-    SCHK(h, h->group > 1 ? pv_launch_link(h->log2n, p, h->group, h->stream) : pv_launch_stretch(h->log2n, p, h->stream));
+    if (d_rst) SCHK(h, pv_launch_stretch_reset(h->log2n, p, h->group, d_rst, rst_stride, h->stream));
+    else SCHK(h, h->group > 1 ? pv_launch_link(h->log2n, p, h->group, h->stream) : pv_launch_stretch(h->log2n, p, h->stream));
     SCHK(h, hipMemcpyAsync(h->d_state, h->d_state_out, sizeof(float) * (size_t)nch * (size_t)h->stride, hipMemcpyDeviceToDevice, h->stream));
     return PV_OK;
 }
@@ -132,7 +139,7 @@ int check_call(pv_stretch *h, const void *in, const void *out, int32_t nch, int3
 
 // Everything a tempo call may reject, before any device work.  tot[r]: the input total of schedule row r (nrows = 1 for a shared row, else nch).
 int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
-                int64_t in_stride, int64_t out_stride, std::vector<long long> &tot)
+                int64_t in_stride, int64_t out_stride, std::vector<long long> &tot, const uint8_t *resets = nullptr, int64_t reset_stride = 0)
 {
     char msg[256];
     if (!in || !out) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
@@ -174,6 +181,27 @@ int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, 
                 return sfail(h, PV_ERR_ARGUMENT, msg);
             }
     }
+    if (resets) {
+        if (reset_stride != 0 && reset_stride < nframes) {
+            snprintf(msg, sizeof msg, "%s: reset_stride %lld is neither 0 (one row for every channel) nor >= nframes %d", fn, (long long)reset_stride, nframes);
+            return sfail(h, PV_ERR_ARGUMENT, msg);
+        }
+        const int rrows = reset_stride == 0 ? 1 : nch;
+        for (int r = 0; r < rrows; r++) {
+            const uint8_t *row = resets + (size_t)r * (size_t)reset_stride, *first = resets + (size_t)(r - r % h->group) * (size_t)reset_stride;
+            for (int m = 0; m < nframes; m++) {
+                if (row[m] > 1) {
+                    snprintf(msg, sizeof msg, "%s: reset flag %d of channel %d, frame %d is neither 0 nor 1", fn, (int)row[m], r, m);
+                    return sfail(h, PV_ERR_ARGUMENT, msg);
+                }
+                if (row[m] != first[m]) {
+                    snprintf(msg, sizeof msg, "%s: reset rows differ within linked group %d (channels %d .. %d): channel %d, frame %d", fn, r / h->group,
+                             r - r % h->group, r - r % h->group + h->group - 1, r, m);
+                    return sfail(h, PV_ERR_ARGUMENT, msg);
+                }
+            }
+        }
+    }
     if (nch > 1 && (in_stride < most || out_stride < (int64_t)nframes * h->hs)) {
         snprintf(msg, sizeof msg, "%s: channel strides shorter than the largest row's input (%lld) or nframes * synthesis_hop (%lld)", fn, most,
                  (long long)nframes * h->hs);
@@ -184,9 +212,13 @@ int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, 
 
 // Frames [f0, f0 + nf) of every row as a position table, S[r][i] = sum of hops f0 .. f0 + i - 1 of row r, uploaded on h->stream into h->d_pos.
 // The page-locked h_pos is rewritten only once the previous upload has completed, so a device call may follow another before any synchronise.
-int upload_pos(pv_stretch *h, const int32_t *hops, int64_t hop_stride, int nrows, int f0, int nf)
+// With resets: the flags of the same frames as int32 prefix counts, R[r][0] = 0, R[r][i + 1] = R[r][i] + flag, packed behind the table in the same
+// upload; h->d_rst then points at them (rrows rows of nf + 1).
+int upload_pos(pv_stretch *h, const int32_t *hops, int64_t hop_stride, int nrows, int f0, int nf, const uint8_t *resets = nullptr, int64_t reset_stride = 0,
+               int rrows = 0)
 {
-    const size_t words = (size_t)nrows * (size_t)(nf + 1);
+    const size_t pos_words = (size_t)nrows * (size_t)(nf + 1);
+    const size_t words = pos_words + (resets ? ((size_t)rrows * (size_t)(nf + 1) + 1) / 2 : 0);      // two int32 counts per int64 word
     if (h->pos_pending) SCHK(h, hipEventSynchronize(h->pos_done));
     h->pos_pending = false;
     if (words > h->hpos_cap) {
@@ -208,6 +240,17 @@ int upload_pos(pv_stretch *h, const int32_t *hops, int64_t hop_stride, int nrows
         long long *S = h->h_pos + (size_t)r * (size_t)(nf + 1);
         S[0] = 0;
         for (int i = 0; i < nf; i++) S[i + 1] = S[i] + row[i];
+    }
+    h->d_rst = nullptr;
+    if (resets) {
+        int *R0 = (int *)(h->h_pos + pos_words);
+        for (int r = 0; r < rrows; r++) {
+            const uint8_t *row = resets + (size_t)r * (size_t)reset_stride + f0;
+            int *R = R0 + (size_t)r * (size_t)(nf + 1);
+            R[0] = 0;
+            for (int i = 0; i < nf; i++) R[i + 1] = R[i] + row[i];
+        }
+        h->d_rst = (int *)(h->d_pos + pos_words);
     }
     SCHK(h, hipMemcpyAsync(h->d_pos, h->h_pos, words * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     SCHK(h, hipEventRecord(h->pos_done, h->stream));
@@ -306,7 +349,8 @@ int pv_stretch_destroy(pv_stretch *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->pos_done) (void)hipEventDestroy(h->pos_done);
-    void *ptrs[] = {h->d_tw64, h->d_tw32, h->d_hann, h->d_state, h->d_state_out, h->d_sums, h->d_stage_in, h->d_stage_out, h->d_pos};
+    void *ptrs[] = {h->d_tw64, h->d_tw32, h->d_hann, h->d_state, h->d_state_out, h->d_sums, h->d_stage_in, h->d_stage_out, h->d_pos, h->d_onset_in,
+                    h->d_onset_counts};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pos) (void)hipHostFree(h->h_pos);
@@ -388,27 +432,34 @@ int pv_stretch_process(pv_stretch *h, const float *in, float *out, int32_t nch, 
     return PV_OK;
 }
 
-int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
-                            int64_t in_stride, int64_t out_stride)
+}  // extern "C"
+
+namespace {
+
+// pv_tempo_process_device, and with `resets` (a host row of 0 / 1 per frame, the row rule of hops) pv_transient_process_device
+int tempo_device(pv_stretch *h, const char *fn, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                 const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
     if (!slive(h)) return PV_ERR_ARGUMENT;
     std::vector<long long> tot;
-    const int rc = check_tempo(h, "pv_tempo_process_device", d_in, d_out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot);
+    const int rc = check_tempo(h, fn, d_in, d_out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot, resets, reset_stride);
     if (rc != PV_OK) return rc;
     if (nch == 0 || nframes == 0) return PV_OK;
     SCHK(h, hipSetDevice(h->device));
-    const int nrows = hop_stride == 0 ? 1 : nch;
-    const int r = upload_pos(h, hops, hop_stride, nrows, 0, nframes);
+    const int nrows = hop_stride == 0 ? 1 : nch, rrows = reset_stride == 0 ? 1 : nch;
+    const int r = upload_pos(h, hops, hop_stride, nrows, 0, nframes, resets, reset_stride, rrows);
     if (r != PV_OK) return r;
-    return run(h, d_in, d_out, nch, nframes, (long)in_stride, (long)out_stride, h->d_pos, hop_stride == 0 ? 0 : (long)nframes + 1);
+    return run(h, d_in, d_out, nch, nframes, (long)in_stride, (long)out_stride, h->d_pos, hop_stride == 0 ? 0 : (long)nframes + 1, h->d_rst,
+               reset_stride == 0 ? 0 : (long)nframes + 1);
 }
 
-int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
-                     int64_t in_stride, int64_t out_stride)
+// pv_tempo_process, and with `resets` pv_transient_process
+int tempo_host(pv_stretch *h, const char *fn, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+               const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
     if (!slive(h)) return PV_ERR_ARGUMENT;
     std::vector<long long> tot;
-    const int rc = check_tempo(h, "pv_tempo_process", in, out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot);
+    const int rc = check_tempo(h, fn, in, out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot, resets, reset_stride);
     if (rc != PV_OK) return rc;
     if (nch == 0 || nframes == 0) return PV_OK;
     SCHK(h, hipSetDevice(h->device));
@@ -420,7 +471,7 @@ int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, in
         h->stage_in_pitch = h->N;
     }
     // pieces of at most max_frames frames whose every row fits the input staging; each channel row is copied over exactly its own span
-    const int nrows = hop_stride == 0 ? 1 : nch;
+    const int nrows = hop_stride == 0 ? 1 : nch, rrows = reset_stride == 0 ? 1 : nch;
     const long sin = h->stage_in_pitch, sout = (long)h->max_frames * h->hs;
     const size_t opitch = sizeof(float) * (size_t)(nch > 1 ? out_stride : (int64_t)nframes * h->hs);
     std::vector<long long> at((size_t)nrows, 0), span((size_t)nrows);    // per row: input consumed before the piece, and the piece's own
@@ -443,9 +494,10 @@ int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, in
                 SCHK(h, hipMemcpyAsync(h->d_stage_in + (size_t)c * sin, in + (size_t)c * (size_t)in_stride + at[(size_t)c], sizeof(float) * (size_t)span[(size_t)c],
                                        hipMemcpyHostToDevice, h->stream));
         }
-        int r = upload_pos(h, hops, hop_stride, nrows, f0, nf);
+        int r = upload_pos(h, hops, hop_stride, nrows, f0, nf, resets, reset_stride, rrows);
         if (r != PV_OK) return r;
-        r = run(h, h->d_stage_in, h->d_stage_out, nch, nf, sin, sout, h->d_pos, hop_stride == 0 ? 0 : (long)nf + 1);
+        r = run(h, h->d_stage_in, h->d_stage_out, nch, nf, sin, sout, h->d_pos, hop_stride == 0 ? 0 : (long)nf + 1, h->d_rst,
+                reset_stride == 0 ? 0 : (long)nf + 1);
         if (r != PV_OK) return r;
         SCHK(h, hipMemcpy2DAsync(out + (long)f0 * h->hs, opitch, h->d_stage_out, sizeof(float) * sout,
                                  sizeof(float) * (size_t)nf * h->hs, nch, hipMemcpyDeviceToHost, h->stream));
@@ -453,6 +505,127 @@ int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, in
         for (int rr = 0; rr < nrows; rr++) at[(size_t)rr] += span[(size_t)rr];
         f0 += nf;
     }
+    return PV_OK;
+}
+
+// Frames per chain of the onset kernel: one round of resident workgroups, at least 8 frames (each chain transforms one extra frame, m0 - 1)
+int onset_chain(const pv_stretch *h, int groups, int nframes)
+{
+    const size_t lds = pv_stretch_lds_bytes(h->log2n, false);
+    long per_cu = (long)((160 * 1024) / (lds + 2048));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    long chains = per_cu * h->cus / (groups > 0 ? groups : 1);
+    if (chains < 1) chains = 1;
+    long F = (nframes + chains - 1) / chains;
+    if (F < 8) F = 8;
+    if (F > nframes) F = nframes;
+    return (int)F;
+}
+
+int check_onset(pv_stretch *h, const char *fn, const void *in, const void *counts, int32_t nch, int32_t nframes, int64_t in_stride, int64_t count_stride)
+{
+    char msg[256];
+    if (!in || !counts) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
+    if (nch % h->group != 0) {
+        snprintf(msg, sizeof msg, "%s: %d channels are not a whole number of linked groups of %d", fn, nch, h->group);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
+    if ((nch > 1 && in_stride < (int64_t)nframes * h->ha) || (nch > h->group && count_stride < nframes)) {
+        snprintf(msg, sizeof msg, "%s: in_stride below nframes * analysis_hop (%lld) or count_stride below nframes (%d)", fn, (long long)nframes * h->ha, nframes);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
+    return PV_OK;
+}
+
+template <class T>
+int grow(pv_stretch *h, T **buf, size_t *cap, size_t words)
+{
+    if (words <= *cap) return PV_OK;
+    SCHK(h, hipStreamSynchronize(h->stream));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    SCHK(h, hipMalloc(buf, words * sizeof(T)));
+    *cap = words;
+    return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                            int64_t in_stride, int64_t out_stride)
+{
+    return tempo_device(h, "pv_tempo_process_device", d_in, d_out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
+}
+
+int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                     int64_t in_stride, int64_t out_stride)
+{
+    return tempo_host(h, "pv_tempo_process", in, out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
+}
+
+// hops == NULL: every hop equals the floor, as one shared row
+int pv_transient_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                                const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<int32_t> flat;
+    if (!hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
+    return tempo_device(h, "pv_transient_process_device", d_in, d_out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
+}
+
+int pv_transient_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
+                         const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<int32_t> flat;
+    if (!hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
+    return tempo_host(h, "pv_transient_process", in, out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
+}
+
+int pv_onset_strength_device(pv_stretch *h, const float *d_in, int32_t nch, int32_t nframes, int64_t in_stride, int32_t *d_counts, int64_t count_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    const int rc = check_onset(h, "pv_onset_strength_device", d_in, d_counts, nch, nframes, in_stride, count_stride);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, pv_launch_onset_strength(h->log2n, d_in, (long)in_stride, nch, h->group, nframes, h->ha, onset_chain(h, nch / h->group, nframes), h->d_tw64,
+                                     h->d_hann, d_counts, (long)count_stride, h->stream));
+    return PV_OK;
+}
+
+int pv_onset_strength(pv_stretch *h, const float *in, int32_t nch, int32_t nframes, int64_t in_stride, int32_t *counts, int64_t count_stride)
+{
+    if (!slive(h)) return PV_ERR_ARGUMENT;
+    int rc = check_onset(h, "pv_onset_strength", in, counts, nch, nframes, in_stride, count_stride);
+    if (rc != PV_OK) return rc;
+    if (nch == 0 || nframes == 0) return PV_OK;
+    SCHK(h, hipSetDevice(h->device));
+    const int groups = nch / h->group;
+    const size_t n = (size_t)nframes * (size_t)h->ha;
+    if ((rc = grow(h, &h->d_onset_in, &h->onset_in_cap, (size_t)nch * n)) != PV_OK) return rc;
+    if ((rc = grow(h, &h->d_onset_counts, &h->onset_counts_cap, (size_t)groups * (size_t)nframes)) != PV_OK) return rc;
+    SCHK(h, hipMemcpy2DAsync(h->d_onset_in, sizeof(float) * n, in, sizeof(float) * (size_t)(nch > 1 ? in_stride : (int64_t)n), sizeof(float) * n, nch,
+                             hipMemcpyHostToDevice, h->stream));
+    SCHK(h, pv_launch_onset_strength(h->log2n, h->d_onset_in, (long)n, nch, h->group, nframes, h->ha, onset_chain(h, groups, nframes), h->d_tw64, h->d_hann,
+                                     h->d_onset_counts, nframes, h->stream));
+    SCHK(h, hipMemcpy2DAsync(counts, sizeof(int32_t) * (size_t)(groups > 1 ? count_stride : (int64_t)nframes), h->d_onset_counts, sizeof(int32_t) * (size_t)nframes,
+                             sizeof(int32_t) * (size_t)nframes, groups, hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return PV_OK;
+}
+
+// TEST HOOK: how a call of nch channels and nframes frames is cut into chains on this chip
+int pv_transient_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32_t *frames_per_chain, int32_t *halo)
+{
+    if (!slive(h) || nch < 1 || nframes < 1 || nch % h->group != 0) return PV_ERR_ARGUMENT;
+    if (frames_per_chain) *frames_per_chain = pick_chain(h, nch / h->group, nframes);
+    if (halo) *halo = h->halo;
     return PV_OK;
 }
 

@@ -1,5 +1,5 @@
 // pv_stretch_device.h -- device building blocks of the time-stretch kernels (internal), shared by pv_stretch_kernels.hip (one phase track per
-// channel) and pv_link_kernels.hip (one phase track per group of linked channels).
+// channel), pv_link_kernels.hip (one phase track per group of linked channels) and pv_transient_kernels.hip (phase resets, onset strength).
 //
 // The two per-frame blocks of pass B that are not functions -- findPeaks + the region walk, and the locking + inverse + overlap-add -- are the
 // fragments pv_stretch_regions.inc and pv_stretch_synth.inc, included in place in the frame loop of both pass B kernels: as force-inlined
@@ -34,6 +34,33 @@ struct Src {
     const float *in;
     long hl;
     __device__ __forceinline__ float at(long s) const { return s < hl ? hist[s] : in[s - hl]; }
+};
+
+// Sample s of the mix of the G channels starting at a group's first slot: the carried hist (slot stride hist_stride) ++ the input (channel stride
+// in_stride).  One f32 rounding per add, in slot order.  The loads go out MIX_BATCH at a time before their adds: a load-add chain would wait one
+// memory latency per channel.
+constexpr int MIX_BATCH = 4;
+
+struct MixSrc {
+    const float *hist;
+    const float *in;
+    long hl, hist_stride, in_stride;
+    int G;
+    __device__ __forceinline__ float at(long s) const
+    {
+        const float *x = s < hl ? hist + s : in + (s - hl);
+        const long stride = s < hl ? hist_stride : in_stride;
+        float u = 0.0f;
+        for (int i0 = 0; i0 < G; i0 += MIX_BATCH) {
+            float v[MIX_BATCH];
+#pragma unroll
+            for (int i = 0; i < MIX_BATCH; i++) v[i] = i0 + i < G ? x[(i0 + i) * stride] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < MIX_BATCH; i++)
+                if (i0 + i < G) u = i0 + i == 0 ? v[0] : __fadd_rn(u, v[i]);
+        }
+        return u;
+    }
 };
 
 // Where frames sit in the stream.  end(n) = S[n], the input consumed by frames 0 .. n-1; frame m's window starts at S[m + 1] - ha (the newest N samples

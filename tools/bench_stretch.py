@@ -7,6 +7,8 @@ resampled to 0.8x on the host, then the pitch kernel at pitchFactor 1 / 1.25), w
 line runs the mono 1024 shape through pv_tempo_process_device on a handle with floor 205, its schedule sweeping the analysis hop 205 -> 320 -> 205 (mean
 262.5, next to the fixed 256): the per-frame position table against the fixed hop.  The linked lines (pv_link_channels) run the stereo 2048 shape
 with G = 2, the 8-channel 4096 shape with G = 8 and as four stereo pairs (G = 2), each with its ratio to the unlinked line of the same shape.
+The reset line (pv_transient_process_device) is the mono 1024 shape on the floor-205 handle at hop 256 with a hold every 64 frames (a flagged frame and
+three more at hop 320 = hs), with its ratio to the tempo line; the strength line (pv_onset_strength_device) analyses the mono 1024 input at hop 256.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576]
 """
@@ -69,6 +71,36 @@ def tempo_line(torch, phaze_amd, N, lo, hi, hs, T, steps, warmup):
             "hbm_fraction": T * (n / T + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def reset_line(torch, phaze_amd, N, lo, ha, hs, T, steps, warmup):
+    m = np.arange(T) % 64
+    hops = np.where(m < 4, hs, ha).astype(np.int32)                  # a hold of four unit-tempo frames every 64, the first one flagged
+    resets = (m == 0).astype(np.uint8)
+    n = int(hops.astype(np.int64).sum())
+    x = (torch.rand((1, n), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, T * hs), device="cuda")
+    ts = phaze_amd.TimeStretch(N, lo, hs, max_channels=1)
+    stream = torch.cuda.Stream()
+    ts.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ts.process_hops_device(x.data_ptr(), y.data_ptr(), 1, T, hops, n, T * hs, resets=resets), steps, warmup)
+    ts.close()
+    return {"kernel": "pv_transient", "fft": N, "analysis_hop_floor": lo, "analysis_hop_mean": n / T, "synthesis_hop": hs, "resets": int(resets.sum()), "channels": 1,
+            "frames_per_channel": T, "ms_per_launch": round(ms, 4), "frames_per_s": T / (ms * 1e-3), "hbm_fraction": T * (n / T + hs) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
+def strength_line(torch, phaze_amd, N, ha, T, steps, warmup):
+    x = (torch.rand((1, T * ha), device="cuda") - 0.5).contiguous()
+    c = torch.empty((1, T), dtype=torch.int32, device="cuda")
+    ts = phaze_amd.TimeStretch(N, ha, N // 4, max_channels=1)
+    stream = torch.cuda.Stream()
+    ts.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ts.onset_strength_device(x.data_ptr(), 1, T, T * ha, c.data_ptr(), T), steps, warmup)
+    ts.close()
+    return {"kernel": "pv_onset_strength", "fft": N, "analysis_hop": ha, "channels": 1, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
+            "frames_per_s": T / (ms * 1e-3), "hbm_fraction": T * (ha + 1) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -93,6 +125,7 @@ def main():
     ap.add_argument("--no-compare", action="store_true", help="skip the two pitch-kernel comparison lines")
     ap.add_argument("--no-tempo", action="store_true", help="skip the variable-tempo line")
     ap.add_argument("--no-link", action="store_true", help="skip the linked-channel lines")
+    ap.add_argument("--no-transient", action="store_true", help="skip the reset line and the onset-strength line")
     args = ap.parse_args()
     import torch
     import phaze_amd
@@ -108,8 +141,16 @@ def main():
             r = stretch_line(torch, phaze_amd, N, ha, hs, nch, max(t, 1), args.steps, args.warmup, G)
             r["ratio_to_unlinked"] = round(r["frames_per_s"] / unlinked[(N, nch)], 4)
             print(json.dumps(r), flush=True)
+    tempo = None
     if not args.no_tempo:
-        print(json.dumps(tempo_line(torch, phaze_amd, 1024, 205, 320, 320, T, args.steps, args.warmup)), flush=True)
+        tempo = tempo_line(torch, phaze_amd, 1024, 205, 320, 320, T, args.steps, args.warmup)
+        print(json.dumps(tempo), flush=True)
+    if not args.no_transient:
+        r = reset_line(torch, phaze_amd, 1024, 205, 256, 320, T, args.steps, args.warmup)
+        if tempo:
+            r["ratio_to_tempo"] = round(r["frames_per_s"] / tempo["frames_per_s"], 4)
+        print(json.dumps(r), flush=True)
+        print(json.dumps(strength_line(torch, phaze_amd, 1024, 256, T, args.steps, args.warmup)), flush=True)
     if not args.no_compare:
         print(json.dumps(pitch_line(torch, phaze_amd, "pitch headline, same input", 1024, 256, 1, T, 1.5, args.steps, args.warmup)), flush=True)
         # --speed 1.25: 0.8x as many input frames after the host resampler, pitch 1 / 1.25: the same output duration as the 1.25x stretch above

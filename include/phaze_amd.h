@@ -377,6 +377,9 @@ PV_API int64_t pv_transient_plan(const int64_t *onsets, int64_t nonsets, int64_t
 /* TEST HOOK, never needed in production: how this chip cuts a call of nch channels and nframes frames into chains (frames per chain; halo =
  * (N - 1) / synthesis_hop earlier frames each chain recomputes), so that tests can put resets on chain and halo boundaries. */
 PV_API int pv_transient_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32_t *frames_per_chain, int32_t *halo);
+/* TEST HOOK, never needed in production: the frames per chain of a pv_onset_strength call of nch channels and nframes frames on this chip (an onset
+ * chain has no halo: it transforms one frame before its own), so that tests can make a chain longer than the kernel's count batch. */
+PV_API int pv_onset_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32_t *frames_per_chain);
 
 #ifdef __cplusplus
 }

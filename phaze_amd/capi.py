@@ -28,7 +28,7 @@ EXPORTS = [
     "pv_tempo_process", "pv_tempo_process_device",
     "pv_link_channels",
     "pv_transient_process", "pv_transient_process_device", "pv_onset_strength", "pv_onset_strength_device", "pv_transient_plan",
-    "pv_onsets_from_strength", "pv_transient_chain_layout",
+    "pv_onsets_from_strength", "pv_transient_chain_layout", "pv_onset_chain_layout",
 ]
 
 
@@ -150,6 +150,7 @@ def load_library():
     L.pv_onsets_from_strength.argtypes = [ip, C.c_int64, C.c_int32, C.c_int32, C.c_double, lp, C.c_int64]
     L.pv_transient_plan.argtypes = [lp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, bp, C.c_int64]
     L.pv_transient_chain_layout.argtypes = [vp, C.c_int32, C.c_int32, ip, ip]
+    L.pv_onset_chain_layout.argtypes = [vp, C.c_int32, C.c_int32, ip]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -659,6 +660,12 @@ class TimeStretch:
         F, halo = C.c_int32(), C.c_int32()
         self._check(self._L.pv_transient_chain_layout(self._h, nch, nframes, C.byref(F), C.byref(halo)))
         return F.value, halo.value
+
+    def onset_chain_layout(self, nch, nframes):
+        """Frames per chain of an onset_strength call of nch channels and nframes frames on this chip (pv_onset_chain_layout, a test hook)."""
+        F = C.c_int32()
+        self._check(self._L.pv_onset_chain_layout(self._h, nch, nframes, C.byref(F)))
+        return F.value
 
     def process_transients(self, x, tau=0.4, lead=None, hop=None, release=None):
         """Offline stretch that carries attacks through unstretched: onset_strength -> onsets_from_strength(tau) -> transient_plan(lead, release) ->

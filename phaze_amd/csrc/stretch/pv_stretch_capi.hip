@@ -629,6 +629,14 @@ int pv_transient_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32
     return PV_OK;
 }
 
+// TEST HOOK: the frames per chain of an onset-strength call of nch channels and nframes frames on this chip
+int pv_onset_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, int32_t *frames_per_chain)
+{
+    if (!slive(h) || nch < 1 || nframes < 1 || nch % h->group != 0) return PV_ERR_ARGUMENT;
+    if (frames_per_chain) *frames_per_chain = onset_chain(h, nch / h->group, nframes);
+    return PV_OK;
+}
+
 int pv_stretch_export_state(pv_stretch *h, int32_t ch, float *hist, float *acc, uint32_t *phi, uint32_t *psi)
 {
     if (!slive(h)) return PV_ERR_ARGUMENT;

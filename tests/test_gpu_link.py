@@ -87,9 +87,12 @@ def test_identical_channels_are_the_unlinked_output(N, G):
     ts.close(); ref_ts.close()
 
 
-@pytest.mark.parametrize("N", NS)
-@pytest.mark.parametrize("name", EDGES)
-@pytest.mark.parametrize("G", [2, 3, 8])
+# every edge at G = 2, 3, 8, and at one edge the groups that leave the mix's batches of four slots a remainder of 1, 2, 3 and 1 again: 5, 6, 7, 9
+GROUP_CASES = [pytest.param(N, name, G, id=f"{G}-{name}-{N}")
+               for N, name, G in [(N, name, G) for G in (2, 3, 8) for name in EDGES for N in NS] + [(N, "r1.25", G) for G in (5, 6, 7, 9) for N in NS]]
+
+
+@pytest.mark.parametrize("N,name,G", GROUP_CASES)
 def test_group_phases_model_parity_and_downmix(N, name, G, record_property):
     import phaze_amd
     ha, hs = _pairs(N)[name]

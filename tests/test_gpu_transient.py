@@ -3,7 +3,9 @@ TimeStretch.onset_strength, TimeStretch.process_transients): the call forms that
 halo boundary, agreement with pv_tempo_process without resets, parity with the model (tests/transient_model.py), psi == phi after a reset, the
 identity in a hold, the onset counts against the model, and the chain strength -> onsets -> plan -> process end to end.
 
-Chain boundaries depend on the chip: every position is derived from the handle's own frames per chain and halo (TimeStretch.chain_layout)."""
+Chain boundaries depend on the chip: every position is derived from the handle's own frames per chain and halo (TimeStretch.chain_layout).  The
+call forms and the hold identity also run at the edges of the hop axis (HOP_EDGES, transient_model.HOLD_SHAPES); the model parity over that axis is in
+tests/test_gpu_stretch_families.py."""
 import ctypes as C
 
 import numpy as np
@@ -45,27 +47,37 @@ def _whole(n, f):
     return -(-n // f)
 
 
-def _layout(N, f, hs, nch, G):
-    """(T, F, halo): T frames that this chip cuts into >= 3 chains of F frames for a call of nch channels."""
+def _tail(tail, halo):
+    """Frames in the last chain: 7 unless asked for "short" (halo // 2: 1 <= r < halo, shorter than the halo the chain after it would need) or
+    "one" (a chain of a single frame)."""
+    return {"short": max(1, halo // 2), "one": 1}.get(tail, tail)
+
+
+def _layout(N, f, hs, nch, G, tail=7):
+    """(T, F, halo): T = 2 F + r frames that this chip cuts into two chains of F frames and a last one of r = _tail(tail, halo) for a call of nch
+    channels."""
     probe = _handle(N, f, hs, nch, G, 1)
     _, halo = probe.chain_layout(nch, 1)
-    T = 2 * 4 * (halo + 1) + 7
+    r = _tail(tail, halo)
+    T = 2 * 4 * (halo + 1) + r
     F, _ = probe.chain_layout(nch, T)
-    while -(-T // F) < 3:
-        T = 2 * F + 7
+    while T != 2 * F + r:
+        T = 2 * F + r
         F, _ = probe.chain_layout(nch, T)
     probe.close()
-    assert halo == (N - 1) // hs and F >= 4 * (halo + 1) and -(-T // F) >= 3
+    assert halo == (N - 1) // hs and F >= 4 * (halo + 1) and T == 2 * F + r and 1 <= r < F
+    assert tail != "short" or r < halo
     return T, F, halo
 
 
 def reset_patterns(T, F, halo):
     """name -> flagged frames, from the chip's own chain length F and halo: frame 0; the last frame; the last frame of a chain and the first of the
-    next; inside the halo of chains 1 and 2 (one frame, and every frame); two in one chain; every frame."""
+    next; inside the halo of chains 1 and 2 (one frame, and every frame); two in one chain; every frame; the last frame of the next-to-last chain with
+    the last frame of the call (the ONLY frame of the last chain when T = 2 F + 1)."""
     assert halo >= 1
     pats = {"frame0": [0], "last": [T - 1], "chain_edge": [F - 1, F], "halo_one": [F - 1 - (halo - 1) // 2, 2 * F - halo],
             "halo_all": list(range(F - halo, F)) + list(range(2 * F - halo, 2 * F)), "two_in_chain": [F + 1, F + 3], "every": list(range(T)),
-            "mixed": [0, F - halo, F, F + 2, 2 * F - 1, T - 1]}
+            "mixed": [0, F - halo, F, F + 2, 2 * F - 1, T - 1], "tail": [2 * F - 1, T - 1]}
     rows = {}
     for k, v in pats.items():
         r = np.zeros(T, np.uint8)
@@ -86,13 +98,26 @@ def _same_states(a, b):
 
 # ---- 1. every call form gives the same bits, with resets on every kind of boundary ---------------------------------------------------------------------
 
-@pytest.mark.parametrize("N,G,nch", SHAPES)
-def test_reset_positions_bit_exact_over_call_forms(N, G, nch):
+# (N, floor, hs) at the edges of the halo = (N - 1) // hs: 255 (the longest), 127 with a floor that divides nothing, 127 at the largest LDS footprint,
+# 5 with neither hop a divisor of N, 1 (hs = N / 2: "halo_one" and "halo_all" coincide), floor = 1 (hist is N - 1 long, one-sample hops beside hops
+# of N) and floor = N (no carried history)
+HOP_EDGES = [(256, 8, 1), (1024, 7, 8), (8192, 1024, 64), (512, 100, 97), (4096, 64, 2048), (2048, 1, 1024), (2048, 2048, 512)]
+LONG_HALO = HOP_EDGES[:3]                                             # ... also with a last chain shorter than the halo, and of one frame
+
+
+# SHAPES at N // 8, 5 N // 16 (halo 3) under the ids they have always had, then HOP_EDGES unlinked and as a group of 2, then LONG_HALO with the other
+# last chains
+HOP_CASES = [pytest.param(N, G, nch, N // 8, 5 * N // 16, 7, id=f"{N}-{G}-{nch}") for N, G, nch in SHAPES] + \
+            [pytest.param(N, G, 2, f, hs, 7, id=f"{N}-{G}-2-{f}-{hs}") for N, f, hs in HOP_EDGES for G in (1, 2)] + \
+            [pytest.param(N, G, 2, f, hs, t, id=f"{N}-{G}-2-{f}-{hs}-{t}") for N, f, hs in LONG_HALO for G in (1, 2) for t in ("short", "one")]
+
+
+@pytest.mark.parametrize("N,G,nch,f,hs,tail", HOP_CASES)
+def test_reset_positions_bit_exact_over_call_forms(N, G, nch, f, hs, tail):
     import torch
-    f, hs = N // 8, 5 * N // 16
-    T, F, halo = _layout(N, f, hs, nch, G)
+    T, F, halo = _layout(N, f, hs, nch, G, tail)
     hops = schedule("random", f, N, T, seed=N + G)
-    hops[F - halo - 1:F + 2] = hs                                     # a unit-tempo run across the first chain boundary
+    hops[F - halo - 1:F + 2] = max(hs, f)                             # a unit-tempo run across the first chain boundary (hs < floor: a run at the floor)
     P = positions(hops)
     n = int(P[-1])
     x = np.stack([S.make_signal("tonal" if c % 2 == 0 else "noise", c, n) for c in range(nch)])
@@ -110,7 +135,13 @@ def test_reset_positions_bit_exact_over_call_forms(N, G, nch):
         if plain is None:
             ts.reset()
             plain = ts.process_hops(x, hops)
-        assert not np.array_equal(_bits(one), _bits(plain)), name      # the flags did something
+            plain_st = _states(ts, nch)
+        # the flags did something: to the output, and where they cannot, to the state the call leaves (at hs = 1 the one output sample a last frame
+        # writes itself lies under Hann's zero, so a flag on the last frame alone shows in acc and psi only)
+        if hs == 1 and name == "last":
+            assert not all(np.array_equal(u.view(np.uint32), v.view(np.uint32)) for sa, sb in zip(st, plain_st) for u, v in zip(sa, sb)), name
+        else:
+            assert not np.array_equal(_bits(one), _bits(plain)), name
         # one frame per call: chains of one frame
         ts.reset()
         fb = np.concatenate([ts.process_hops(x[:, P[m]:P[m + 1]], hops[m:m + 1], r[m:m + 1]) for m in range(T)], axis=1)
@@ -169,12 +200,11 @@ def test_reset_positions_bit_exact_over_call_forms(N, G, nch):
         h.close()
 
 
-@pytest.mark.parametrize("N,G,nch", SHAPES)
-def test_no_flags_is_the_tempo_call(N, G, nch):
+@pytest.mark.parametrize("N,G,nch,f,hs,tail", HOP_CASES)
+def test_no_flags_is_the_tempo_call(N, G, nch, f, hs, tail):
     """resets = None and all-zero flags (the reset kernels with nothing to do) both give the bits and the state of pv_tempo_process; hops = None
     with flags is the fixed-hop call."""
-    f, hs = N // 8, 5 * N // 16
-    T, F, halo = _layout(N, f, hs, nch, G)
+    T, F, halo = _layout(N, f, hs, nch, G, tail)
     hops = schedule("random", f, N, T, seed=7)
     n = int(hops.sum())
     x = np.stack([S.make_signal("noise" if c % 2 == 0 else "tonal", c, max(n, T * f)) for c in range(nch)])
@@ -328,7 +358,7 @@ def test_psi_is_phi_after_a_reset_and_through_a_unit_tempo_hold(N, G, nch):
 # ---- 3. identity in a hold -----------------------------------------------------------------------------------------------------------------------------
 
 def _hold_case(N, ha, hs, seed):
-    J, pre = 2 * -(-N // hs) + 4, -(-N // ha) + 3
+    J, pre = TM.hold_base(N, ha, hs)
     hops, resets, r = TM.hold_schedule(N, ha, hs, pre, J)
     x = np.random.default_rng(seed).standard_normal(int(hops.sum())).astype(np.float32)
     return hops, resets, r, J, x
@@ -372,7 +402,9 @@ def test_hold_identity_linked_pair(N, ha, hs, record_property):
 
 # ---- 4. onset strength ---------------------------------------------------------------------------------------------------------------------------------
 
-ONSET_SHAPES = [(1024, 256), (2048, 256), (4096, 1024), (256, 100), (8192, 1024), (512, 128)]
+# the last six: the edges of the hop the header allows (1 .. N): ha = 1, 2 (>= 5000 frames each), 8, ha = N, and a hop that divides nothing
+ONSET_SHAPES = [(1024, 256), (2048, 256), (4096, 1024), (256, 100), (8192, 1024), (512, 128), (256, 1), (256, 2), (256, 8), (512, 512), (8192, 8192),
+                (1024, 255)]
 
 
 def _onset_input(N, name):
@@ -399,7 +431,8 @@ def test_onset_strength_against_the_model(N, ha, record_property):
     assert tot <= 0.01 * frames, (tot, frames)
 
 
-@pytest.mark.parametrize("N,ha,G,nch", [(1024, 256, 2, 4), (512, 128, 3, 3), (2048, 256, 8, 8)])
+@pytest.mark.parametrize("N,ha,G,nch", [(1024, 256, 2, 4), (512, 128, 3, 3), (2048, 256, 8, 8), (1024, 256, 5, 10), (256, 100, 6, 6), (4096, 1024, 7, 7),
+                                        (512, 128, 9, 18)])
 def test_onset_strength_of_groups_is_mono_on_the_mix(N, ha, G, nch):
     n = 60 * ha + 17
     x = np.stack([TM.class_signal("bursts_tones", n, N, [5 * N + 11 * c, 9 * N + 300], seed=c) for c in range(nch)])

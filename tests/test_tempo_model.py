@@ -8,7 +8,7 @@ import pytest
 
 import tones as TN
 from stretch_model import StretchModel
-from tempo_model import TONE_SHAPES, TempoModel, positions, schedule, switch_bounds, tone_schedule_input
+from tempo_model import TONE_SHAPES, TONE_SHAPES_EDGES, TempoModel, positions, schedule, switch_bounds, tone_schedule_input
 
 
 def _bits(a):
@@ -74,10 +74,11 @@ def test_all_floor_schedule_is_process():
 # ---- stationary tones under any schedule --------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("kind", ["ramp", "random", "alt"])
-@pytest.mark.parametrize("sid", list(TONE_SHAPES))
+@pytest.mark.parametrize("sid", list(TONE_SHAPES) + list(TONE_SHAPES_EDGES))
 def test_tones_closed_form_under_schedules(sid, kind):
-    """The synthesis phase of a steady partial advances by f hs / N per frame whatever ha_m is, so the fixed-hop gate of 3e-6 holds."""
-    N, floor, hs, freqs, amps = TONE_SHAPES[sid]
+    """The synthesis phase of a steady partial advances by f hs / N per frame whatever ha_m is, so the fixed-hop gate of 3e-6 holds: also at the hop
+    edges (halo 1 .. 255, hs = 1, hs = N / 2, hops that divide nothing)."""
+    N, floor, hs, freqs, amps = {**TONE_SHAPES, **TONE_SHAPES_EDGES}[sid]
     TN.check_partials(N, freqs)
     hops, x = tone_schedule_input(N, floor, hs, freqs, amps, kind)
     y = TempoModel(N, floor, hs).process_hops(x[None, :], hops)[0]

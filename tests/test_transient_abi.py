@@ -1,5 +1,5 @@
 """CPU checks of the transient surface: the header declares and the library exports pv_transient_process / _device, pv_onset_strength / _device,
-pv_transient_plan, pv_onsets_from_strength and the chain-layout test hook with the argument types the ctypes binding gives them, the ABI stays 6, the
+pv_transient_plan, pv_onsets_from_strength and the two chain-layout test hooks with the argument types the ctypes binding gives them, the ABI stays 6, the
 C planner and onset rule agree exactly with the numpy ones (tests/transient_model.py), no new kernel instance spills a VGPR or uses scratch, the
 instances that existed keep the resources of the commit before this feature, and examples/pv_transient.c builds as pedantic C99 (and, on a GPU, runs)."""
 import ctypes as C
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "phaze_amd.h")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 SURFACE = {"pv_transient_process": 11, "pv_transient_process_device": 11, "pv_onset_strength": 7, "pv_onset_strength_device": 7, "pv_transient_plan": 12,
-           "pv_onsets_from_strength": 7, "pv_transient_chain_layout": 5}
+           "pv_onsets_from_strength": 7, "pv_transient_chain_layout": 5, "pv_onset_chain_layout": 4}
 
 
 def _lib():
@@ -71,6 +71,7 @@ def test_transient_calls_without_a_handle_are_rejected():
     assert L.pv_onset_strength(None, x, 1, 2, 8, c, 2) == capi.PV_ERR_ARGUMENT
     assert L.pv_onset_strength_device(None, None, 1, 2, 8, None, 2) == capi.PV_ERR_ARGUMENT
     assert L.pv_transient_chain_layout(None, 1, 1, None, None) == capi.PV_ERR_ARGUMENT
+    assert L.pv_onset_chain_layout(None, 1, 1, None) == capi.PV_ERR_ARGUMENT
 
 
 # ---- the host planner and onset rule against the numpy ones ---------------------------------------------------------------------------------

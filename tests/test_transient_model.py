@@ -11,12 +11,19 @@ HOLD_GATE = 2e-7          # relative RMS: 4 x the 5.4e-8 the prototype measured,
 HOLD_POWER = 0.5          # without the reset the same comparison must exceed this (1.2 .. 1.4 measured)
 
 
+def hold_gate(N, hs):
+    """HOLD_GATE, and where many frames overlap the f32 accumulator's own rounding: an output sample is the sum of ceil(N / hs) frames, one f32
+    addition each, and every addition rounds by up to 2^-24 of a partial sum no larger than the result; independent roundings add in RMS, so the
+    accumulator alone leaves 2^-24 sqrt(ceil(N / hs)): 9.5e-7 at 256 / 1, 6.7e-7 at 8192 / 64, 3.4e-7 at 512 / 16, below HOLD_GATE up to 11 frames."""
+    return max(HOLD_GATE, 2.0 ** -24 * np.sqrt(-(-N // hs)))
+
+
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _hold_case(N, ha, hs, seed=1):
-    J, pre = 2 * -(-N // hs) + 4, -(-N // ha) + 3
+    J, pre = TM.hold_base(N, ha, hs)
     hops, resets, r = TM.hold_schedule(N, ha, hs, pre, J)
     x = np.random.default_rng(seed).standard_normal(int(hops.sum())).astype(np.float32)
     return hops, resets, r, J, x
@@ -25,7 +32,8 @@ def _hold_case(N, ha, hs, seed=1):
 @pytest.mark.parametrize("N,ha,hs", TM.HOLD_SHAPES)
 def test_a_hold_that_starts_with_a_reset_is_the_input(N, ha, hs, record_property):
     """Reset at frame r, hops = hs for r .. r + J, Gaussian noise: every output sample that only frames r .. r + J write is g(n) x[n + delta].
-    Measured 4.6e-8 .. 5.5e-8 with the reset and 1.2 .. 1.4 without."""
+    Measured 4.2e-8 .. 5.5e-8 with the reset where at most 11 frames overlap, 8.8e-8 at 512 / 16, 1.8e-7 at 8192 / 64 and 2.4e-7 at 256 / 1
+    (gate: hold_gate), and 1.2 .. 1.4 without."""
     hops, resets, r, J, x = _hold_case(N, ha, hs)
     floor = min(ha, hs)
     y = TM.TransientModel(N, floor, hs).process_hops(x[None], hops, resets)[0]
@@ -34,7 +42,7 @@ def test_a_hold_that_starts_with_a_reset_is_the_input(N, ha, hs, record_property
     record_property("with_reset", with_reset)
     record_property("without", without)
     print(f"hold identity N={N} ha={ha} hs={hs}: {with_reset:.3e} with the reset, {without:.3f} without")
-    assert with_reset <= HOLD_GATE, with_reset
+    assert with_reset <= hold_gate(N, hs), with_reset
     assert without > HOLD_POWER, without
 
 
@@ -179,3 +187,19 @@ def test_gpu_onset_inputs_have_at_most_one_percent_near_ties():
             c, d = TM.onset_strength(_onset_input(N, name), N, ha)
             tot, frames = tot + int(d.sum()), frames + c.size
         assert tot <= 0.01 * frames, (N, ha, tot, frames)
+
+
+def _family_cases():
+    import test_gpu_stretch_families as F
+    cases = [(N, name, 1, "noise", sched, False) for N, name, sched in F.SCHEDULE_CASES]
+    cases += [(N, name, G, "tonal", "random", True) for N, name, G in F.RESET_CASES] + [(N, name, G, None, "random", False) for N, name, G in F.LINK_CASES]
+    return [c for c in cases if c[0] <= 512]
+
+
+@pytest.mark.parametrize("N,name,G,kind,sched,flags", _family_cases())
+def test_gpu_family_inputs_leave_out_at_most_one_percent_of_frames_and_one(N, name, G, kind, sched, flags):
+    """The cap of tests/test_gpu_stretch_families.py on the model's doubtful frames, at the sizes that run here in seconds (N <= 512)."""
+    import test_gpu_stretch_families as F
+    floor, hs, T, hops, resets, hist, x = F.family_case(N, name, G, kind, sched, flags)
+    _, m = F.family_model(N, floor, hs, G, hops, resets, hist, x)
+    assert np.count_nonzero(m.doubtful[0]) <= 0.01 * T + 1

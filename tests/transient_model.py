@@ -144,7 +144,30 @@ def hold_identity(y, x, hops, N, hs, r, J):
     return float(np.sqrt(np.mean((got - want) ** 2)) / np.sqrt(np.mean(want ** 2)))
 
 
-HOLD_SHAPES = [(1024, 256, 384), (1024, 256, 320), (2048, 512, 300), (256, 100, 97)]      # (N, ha, hs)
+# (N, ha, hs): halo = (N - 1) // hs of 2, 3, 6, 2, and from (512, 128, 16) on 31, 255, 3, 3, 127, 1, 1; ha = N (no carried history), hs = N / 2, hs = 1
+HOLD_SHAPES = [(1024, 256, 384), (1024, 256, 320), (2048, 512, 300), (256, 100, 97), (512, 128, 16), (256, 8, 1), (4096, 1024, 1280),
+               (8192, 2048, 2560), (8192, 1024, 64), (2048, 2048, 1024), (1024, 256, 512)]
+
+
+def hold_base(N, ha, hs):
+    """(J, pre) of the shortest hold case: 2 ceil(N / hs) + 4 held frames after the reset, ceil(N / ha) + 3 frames at ha on either side."""
+    return 2 * -(-N // hs) + 4, -(-N // ha) + 3
+
+
+# ---- a linked pair of tones ------------------------------------------------------------------------------------------------------------------
+
+PAIR_AMPS, PAIR_PHASES = (0.5, 0.2), (0.4, 2.1)
+
+
+def tone_pair_input(N, floor, hs, freq, kind="random", seed=0):
+    """(hops, float32[2, sum hops]): one partial at `freq` bins in two channels with amplitudes PAIR_AMPS and phases PAIR_PHASES under a schedule
+    floor .. N, long enough for 8 N of steady output (tempo_model.tone_schedule_input).  A linked pair keeps the phase difference 2.1 - 0.4."""
+    from tempo_model import schedule
+    lo, _ = TN.steady_range(N, floor, hs, 0)
+    T = -(-(lo + 9 * N) // hs)
+    hops = schedule(kind, floor, N, T, seed)
+    n = int(hops.sum())
+    return hops, np.stack([TN.partials(N, [freq], [a], [p], n) for a, p in zip(PAIR_AMPS, PAIR_PHASES)])
 
 
 # ---- onset strength -------------------------------------------------------------------------------------------------------------------------

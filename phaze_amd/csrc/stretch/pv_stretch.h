@@ -19,7 +19,7 @@ struct PvStretchParams {
     const float *state_in;    // [nch][state_stride] carried state in
     float *state_out;         // [nch][state_stride] carried state out (the host copies it back behind the launch)
     long state_stride;
-    unsigned *sums;           // [nch][nchains][2][H]: pass A writes {main, halo} advance sums, the scan turns the halo slot into pass B's start carry
+    unsigned *sums;           // [groups][nchains][2][H]: pass A writes {main, halo} advance sums, the scan turns the halo slot into pass B's start carry
     const double2 *tw64;      // exp(-2 pi j k / N), k in [0, N)
     const float2 *tw32;
     const float *hann;        // periodic Hann, f32, N values
@@ -31,18 +31,12 @@ struct PvStretchParams {
 bool pv_stretch_supported(int log2n);                     // N = 256 .. 8192
 size_t pv_stretch_lds_bytes(int log2n, bool pass_b);
 int pv_stretch_threads();
-// pass A + scan + pass B on `st`; the caller then copies state_out back into its state
-hipError_t pv_launch_stretch(int log2n, const PvStretchParams &p, hipStream_t st);
-// the scan alone (pv_stretch_scan over p.nch slots of p.state_stride floats): linked channels run it once per group
-hipError_t pv_launch_stretch_scan(int log2n, const PvStretchParams &p, hipStream_t st);
-// linked channels (pv_link_kernels.hip), G >= 2 consecutive slots per group, p.nch a multiple of G: pass A per (chain, group), the scan per group,
-// pass B per (chain, channel); p.sums holds [nch / G][nchains][2][H]
-hipError_t pv_launch_link(int log2n, const PvStretchParams &p, int G, hipStream_t st);
-// phase resets (pv_transient_kernels.hip): the schedule passes with psi := q at flagged frames.  p.pos must be set; rst holds int32 prefix counts of the
-// flags, [rows][nframes + 1] (R[0] = 0, R[m + 1] - R[m] = frame m's flag), row of slot c at rst + c * rst_stride (0: one row for every slot).  G = 1:
-// unlinked, G >= 2: linked groups (the row of slot g G); p.sums holds [nch / G][nchains][2][H]
-hipError_t pv_launch_stretch_reset(int log2n, const PvStretchParams &p, int G, const int *rst, long rst_stride, hipStream_t st);
-// onset strength (pv_transient_kernels.hip): counts[g * count_stride + m] for the nch / G groups of `in` (channel c at in + c * in_stride, nframes * ha
+// pass A + scan + pass B on `st`; the caller then copies state_out back into its state.  G = 1: every slot on its own; G >= 2: linked groups of G
+// consecutive slots, p.nch a multiple of G (pass A and the scan run per group, pass B per channel).  p.sums holds [nch / G][nchains][2][H].
+// rst != nullptr: phase resets, psi := q at flagged frames (p.pos must be set).  rst holds int32 prefix counts of the flags, [rows][nframes + 1]
+// (R[0] = 0, R[m + 1] - R[m] = frame m's flag), the row of slot c at rst + c * rst_stride (0: one row for every slot); a group reads the row of slot g G.
+hipError_t pv_launch_stretch(int log2n, const PvStretchParams &p, int G, const int *rst, long rst_stride, hipStream_t st);
+// onset strength (pv_onset_kernels.hip): counts[g * count_stride + m] for the nch / G groups of `in` (channel c at in + c * in_stride, nframes * ha
 // samples), one workgroup per (chain of F frames, group); stateless
 hipError_t pv_launch_onset_strength(int log2n, const float *in, long in_stride, int nch, int G, int nframes, int ha, int F, const double2 *tw64,
                                     const float *hann, int *counts, long count_stride, hipStream_t st);

@@ -3,9 +3,9 @@
 // Owns one time-stretch handle's device state -- per channel slot hist[N - ha] | acc[N - hs] | phi[H] | psi[H] (pv_stretch.h) -- and turns calls
 // into pass A + scan + pass B launches (pv_stretch_kernels.hip).  No CPU compute path: without a HIP device pv_stretch_create fails with PV_ERR_DEVICE.
 // pv_tempo_process / pv_tempo_process_device (variable tempo) turn a host schedule of per-frame hops into the kernels' position table.
-// pv_link_channels groups consecutive slots: a linked handle runs pv_link_kernels.hip (one phase track per group) in place of the unlinked passes.
-// pv_transient_process / pv_transient_process_device add a host row of per-frame reset flags (pv_transient_kernels.hip), uploaded as prefix counts behind
-// the position table; pv_onset_strength runs the stateless detection kernel of the same file.
+// pv_link_channels groups consecutive slots: a linked handle runs the LINK instances of the passes (one phase track per group).
+// pv_transient_process / pv_transient_process_device add a host row of per-frame reset flags (the RESET instances), uploaded as prefix counts behind
+// the position table; pv_onset_strength runs the stateless detection kernel of pv_onset_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -73,20 +73,44 @@ int sfail_hip(pv_stretch *h, hipError_t e, const char *what)
 
 bool slive(const pv_stretch *h) { return h && h->magic == kStretchMagic; }
 
-// Frames per chain: one round of the workgroups the chip holds at once, but never fewer than four times the (halo + 1) frames a chain recomputes.
-int pick_chain(const pv_stretch *h, int nch, int nframes)
+// Frames per chain: one round of the workgroups the chip holds at once (each takes `lds` + `pad` bytes of a CU's LDS, at most 8 per CU) over `groups`
+// rows of the grid, but never fewer than min_frames.
+int chain_frames(const pv_stretch *h, size_t lds, size_t pad, int groups, int nframes, long min_frames)
 {
-    const size_t lds = pv_stretch_lds_bytes(h->log2n, true);
-    long per_cu = (long)((160 * 1024) / (lds + 512));
+    long per_cu = (long)((160 * 1024) / (lds + pad));
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
-    const long slots = per_cu * h->cus;
-    long chains = slots / (nch > 0 ? nch : 1);
+    long chains = per_cu * h->cus / (groups > 0 ? groups : 1);
     if (chains < 1) chains = 1;
     long F = (nframes + chains - 1) / chains;
-    if (F < 4L * (h->halo + 1)) F = 4L * (h->halo + 1);
+    if (F < min_frames) F = min_frames;
     if (F > nframes) F = nframes;
     return (int)F;
+}
+
+// the stretch passes: never fewer than four times the (halo + 1) frames a chain recomputes
+int pick_chain(const pv_stretch *h, int groups, int nframes)
+{
+    return chain_frames(h, pv_stretch_lds_bytes(h->log2n, true), 512, groups, nframes, 4L * (h->halo + 1));
+}
+
+// the onset kernel: at least 8 frames (each chain transforms one extra frame, m0 - 1)
+int onset_chain(const pv_stretch *h, int groups, int nframes)
+{
+    return chain_frames(h, pv_stretch_lds_bytes(h->log2n, false), 2048, groups, nframes, 8);
+}
+
+// Grows a device buffer to `words` elements, contents not kept; a launch in flight may still use the old buffer.
+template <class T>
+int grow(pv_stretch *h, T **buf, size_t *cap, size_t words)
+{
+    if (words <= *cap) return PV_OK;
+    SCHK(h, hipStreamSynchronize(h->stream));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    SCHK(h, hipMalloc(buf, words * sizeof(T)));
+    *cap = words;
+    return PV_OK;
 }
 
 // One launch over channel slots [0, nch): device pointers, asynchronous on h->stream.  d_pos: the position table of a tempo call (pv_stretch.h), or
@@ -105,31 +129,32 @@ int run(pv_stretch *h, const float *d_in, float *d_out, int nch, int nframes, lo
     p.state_in = h->d_state; p.state_out = h->d_state_out; p.state_stride = h->stride;
     p.tw64 = h->d_tw64; p.tw32 = h->d_tw32; p.hann = h->d_hann;
     p.pos = d_pos; p.pos_stride = pos_stride;
-    const size_t words = (size_t)(nch / h->group) * (size_t)p.nchains * 2 * (size_t)h->H;
-    if (words > h->sums_cap) {
-        SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still use the old buffer
-        if (h->d_sums) (void)hipFree(h->d_sums);
-        h->d_sums = nullptr; h->sums_cap = 0;
-        SCHK(h, hipMalloc(&h->d_sums, words * sizeof(unsigned)));
-        h->sums_cap = words;
-    }
+    const int rc = grow(h, &h->d_sums, &h->sums_cap, (size_t)(nch / h->group) * (size_t)p.nchains * 2 * (size_t)h->H);
+    if (rc != PV_OK) return rc;
     p.sums = h->d_sums;
-    if (d_rst) SCHK(h, pv_launch_stretch_reset(h->log2n, p, h->group, d_rst, rst_stride, h->stream));
-    else SCHK(h, h->group > 1 ? pv_launch_link(h->log2n, p, h->group, h->stream) : pv_launch_stretch(h->log2n, p, h->stream));
+    SCHK(h, pv_launch_stretch(h->log2n, p, h->group, d_rst, rst_stride, h->stream));
     SCHK(h, hipMemcpyAsync(h->d_state, h->d_state_out, sizeof(float) * (size_t)nch * (size_t)h->stride, hipMemcpyDeviceToDevice, h->stream));
+    return PV_OK;
+}
+
+// What every call checks first: the two buffers, the counts, the capacity, whole linked groups.  fn: the name the message opens with.
+int check_buffers(pv_stretch *h, const char *fn, const void *a, const void *b, int32_t nch, int32_t nframes)
+{
+    char msg[256];
+    if (!a || !b) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
+    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
+    if (nch % h->group != 0) {
+        snprintf(msg, sizeof msg, "%s: %d channels are not a whole number of linked groups of %d", fn, nch, h->group);
+        return sfail(h, PV_ERR_ARGUMENT, msg);
+    }
     return PV_OK;
 }
 
 int check_call(pv_stretch *h, const void *in, const void *out, int32_t nch, int32_t nframes, int64_t in_stride, int64_t out_stride)
 {
-    if (!in || !out) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: null buffer");
-    if (nch < 0 || nframes < 0) return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: negative channel or frame count");
-    if (nch > h->max_channels) return sfail(h, PV_ERR_CAPACITY, "pv_stretch_process: more channels than max_channels");
-    if (nch % h->group != 0) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "pv_stretch_process: %d channels are not a whole number of linked groups of %d", nch, h->group);
-        return sfail(h, PV_ERR_ARGUMENT, msg);
-    }
+    const int rc = check_buffers(h, "pv_stretch_process", in, out, nch, nframes);
+    if (rc != PV_OK) return rc;
     if (nch > 1 && (in_stride < (int64_t)nframes * h->ha || out_stride < (int64_t)nframes * h->hs))
         return sfail(h, PV_ERR_ARGUMENT, "pv_stretch_process: channel strides shorter than nframes * hop");
     return PV_OK;
@@ -142,13 +167,8 @@ int check_tempo(pv_stretch *h, const char *fn, const void *in, const void *out, 
                 int64_t in_stride, int64_t out_stride, std::vector<long long> &tot, const uint8_t *resets = nullptr, int64_t reset_stride = 0)
 {
     char msg[256];
-    if (!in || !out) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
-    if (nch % h->group != 0) {
-        snprintf(msg, sizeof msg, "%s: %d channels are not a whole number of linked groups of %d", fn, nch, h->group);
-        return sfail(h, PV_ERR_ARGUMENT, msg);
-    }
+    const int rc = check_buffers(h, fn, in, out, nch, nframes);
+    if (rc != PV_OK) return rc;
     if (nframes > 0 && !hops) { snprintf(msg, sizeof msg, "%s: null hops", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
     if (hop_stride != 0 && hop_stride < nframes) {
         snprintf(msg, sizeof msg, "%s: hop_stride %lld is neither 0 (one row for every channel) nor >= nframes %d", fn, (long long)hop_stride, nframes);
@@ -227,13 +247,8 @@ int upload_pos(pv_stretch *h, const int32_t *hops, int64_t hop_stride, int nrows
         SCHK(h, hipHostMalloc((void **)&h->h_pos, words * sizeof(long long), hipHostMallocDefault));
         h->hpos_cap = words;
     }
-    if (words > h->pos_cap) {
-        SCHK(h, hipStreamSynchronize(h->stream));                      // a launch in flight may still read the old table
-        if (h->d_pos) (void)hipFree(h->d_pos);
-        h->d_pos = nullptr; h->pos_cap = 0;
-        SCHK(h, hipMalloc(&h->d_pos, words * sizeof(long long)));
-        h->pos_cap = words;
-    }
+    const int rc = grow(h, &h->d_pos, &h->pos_cap, words);
+    if (rc != PV_OK) return rc;
     if (!h->pos_done) SCHK(h, hipEventCreateWithFlags(&h->pos_done, hipEventDisableTiming));
     for (int r = 0; r < nrows; r++) {
         const int32_t *row = hops + (size_t)r * (size_t)hop_stride + f0;
@@ -436,11 +451,14 @@ int pv_stretch_process(pv_stretch *h, const float *in, float *out, int32_t nch, 
 
 namespace {
 
-// pv_tempo_process_device, and with `resets` (a host row of 0 / 1 per frame, the row rule of hops) pv_transient_process_device
-int tempo_device(pv_stretch *h, const char *fn, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
-                 const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
+// pv_tempo_process_device, and with `resets` (a host row of 0 / 1 per frame, the row rule of hops) pv_transient_process_device.  transient: the
+// entry point takes hops == NULL for "every hop equals the floor, as one shared row"
+int tempo_device(pv_stretch *h, const char *fn, bool transient, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops,
+                 int64_t hop_stride, const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
     if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<int32_t> flat;
+    if (transient && !hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
     std::vector<long long> tot;
     const int rc = check_tempo(h, fn, d_in, d_out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot, resets, reset_stride);
     if (rc != PV_OK) return rc;
@@ -454,20 +472,21 @@ int tempo_device(pv_stretch *h, const char *fn, const float *d_in, float *d_out,
 }
 
 // pv_tempo_process, and with `resets` pv_transient_process
-int tempo_host(pv_stretch *h, const char *fn, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
-               const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
+int tempo_host(pv_stretch *h, const char *fn, bool transient, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops,
+               int64_t hop_stride, const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
     if (!slive(h)) return PV_ERR_ARGUMENT;
+    std::vector<int32_t> flat;
+    if (transient && !hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
     std::vector<long long> tot;
     const int rc = check_tempo(h, fn, in, out, nch, nframes, hops, hop_stride, in_stride, out_stride, tot, resets, reset_stride);
     if (rc != PV_OK) return rc;
     if (nch == 0 || nframes == 0) return PV_OK;
     SCHK(h, hipSetDevice(h->device));
     if (h->stage_in_pitch < h->N) {                                    // max_frames * ha < N: one frame of hop N must fit a piece
-        SCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_stage_in);
-        h->d_stage_in = nullptr;
-        SCHK(h, hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)h->max_channels * (size_t)h->N));
+        size_t cap = 0;                                                // (regrown whatever it holds)
+        const int rg = grow(h, &h->d_stage_in, &cap, (size_t)h->max_channels * (size_t)h->N);
+        if (rg != PV_OK) return rg;
         h->stage_in_pitch = h->N;
     }
     // pieces of at most max_frames frames whose every row fits the input staging; each channel row is copied over exactly its own span
@@ -508,47 +527,15 @@ int tempo_host(pv_stretch *h, const char *fn, const float *in, float *out, int32
     return PV_OK;
 }
 
-// Frames per chain of the onset kernel: one round of resident workgroups, at least 8 frames (each chain transforms one extra frame, m0 - 1)
-int onset_chain(const pv_stretch *h, int groups, int nframes)
-{
-    const size_t lds = pv_stretch_lds_bytes(h->log2n, false);
-    long per_cu = (long)((160 * 1024) / (lds + 2048));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    long chains = per_cu * h->cus / (groups > 0 ? groups : 1);
-    if (chains < 1) chains = 1;
-    long F = (nframes + chains - 1) / chains;
-    if (F < 8) F = 8;
-    if (F > nframes) F = nframes;
-    return (int)F;
-}
-
 int check_onset(pv_stretch *h, const char *fn, const void *in, const void *counts, int32_t nch, int32_t nframes, int64_t in_stride, int64_t count_stride)
 {
     char msg[256];
-    if (!in || !counts) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return sfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return sfail(h, PV_ERR_CAPACITY, msg); }
-    if (nch % h->group != 0) {
-        snprintf(msg, sizeof msg, "%s: %d channels are not a whole number of linked groups of %d", fn, nch, h->group);
-        return sfail(h, PV_ERR_ARGUMENT, msg);
-    }
+    const int rc = check_buffers(h, fn, in, counts, nch, nframes);
+    if (rc != PV_OK) return rc;
     if ((nch > 1 && in_stride < (int64_t)nframes * h->ha) || (nch > h->group && count_stride < nframes)) {
         snprintf(msg, sizeof msg, "%s: in_stride below nframes * analysis_hop (%lld) or count_stride below nframes (%d)", fn, (long long)nframes * h->ha, nframes);
         return sfail(h, PV_ERR_ARGUMENT, msg);
     }
-    return PV_OK;
-}
-
-template <class T>
-int grow(pv_stretch *h, T **buf, size_t *cap, size_t words)
-{
-    if (words <= *cap) return PV_OK;
-    SCHK(h, hipStreamSynchronize(h->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    SCHK(h, hipMalloc(buf, words * sizeof(T)));
-    *cap = words;
     return PV_OK;
 }
 
@@ -559,32 +546,26 @@ extern "C" {
 int pv_tempo_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
                             int64_t in_stride, int64_t out_stride)
 {
-    return tempo_device(h, "pv_tempo_process_device", d_in, d_out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
+    return tempo_device(h, "pv_tempo_process_device", false, d_in, d_out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
 }
 
 int pv_tempo_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
                      int64_t in_stride, int64_t out_stride)
 {
-    return tempo_host(h, "pv_tempo_process", in, out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
+    return tempo_host(h, "pv_tempo_process", false, in, out, nch, nframes, hops, hop_stride, nullptr, 0, in_stride, out_stride);
 }
 
 // hops == NULL: every hop equals the floor, as one shared row
 int pv_transient_process_device(pv_stretch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
                                 const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
-    if (!slive(h)) return PV_ERR_ARGUMENT;
-    std::vector<int32_t> flat;
-    if (!hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
-    return tempo_device(h, "pv_transient_process_device", d_in, d_out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
+    return tempo_device(h, "pv_transient_process_device", true, d_in, d_out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
 }
 
 int pv_transient_process(pv_stretch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
                          const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride)
 {
-    if (!slive(h)) return PV_ERR_ARGUMENT;
-    std::vector<int32_t> flat;
-    if (!hops && nframes > 0) { flat.assign((size_t)nframes, h->ha); hops = flat.data(); hop_stride = 0; }
-    return tempo_host(h, "pv_transient_process", in, out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
+    return tempo_host(h, "pv_transient_process", true, in, out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride);
 }
 
 int pv_onset_strength_device(pv_stretch *h, const float *d_in, int32_t nch, int32_t nframes, int64_t in_stride, int32_t *d_counts, int64_t count_stride)

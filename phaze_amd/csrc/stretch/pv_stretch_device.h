@@ -1,14 +1,14 @@
-// pv_stretch_device.h -- device building blocks of the time-stretch kernels (internal), shared by pv_stretch_kernels.hip (one phase track per
-// channel), pv_link_kernels.hip (one phase track per group of linked channels) and pv_transient_kernels.hip (phase resets, onset strength).
+// pv_stretch_device.h -- device building blocks of the time-stretch kernels (internal), shared by pv_stretch_kernels.hip (pass A, the scans, pass B)
+// and pv_onset_kernels.hip (onset strength), and the log2n dispatch of their launchers.
 //
-// The two per-frame blocks of pass B that are not functions -- findPeaks + the region walk, and the locking + inverse + overlap-add -- are the
-// fragments pv_stretch_regions.inc and pv_stretch_synth.inc, included in place in the frame loop of both pass B kernels: as force-inlined
-// functions they changed the register allocation and instruction selection of the existing instances, as fragments they compile to the
-// same ISA as the code they replaced.
+// The two big per-frame blocks of pass B -- findPeaks + the region walk, and the locking + inverse + overlap-add -- are plain code in the one frame
+// loop of pv_stretch_pass_b, not functions here: as force-inlined functions they changed the register allocation and instruction selection.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pv_stretch.h"
 
@@ -16,6 +16,18 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int NOPEAK = 0x7fffffff;
+
+// f(std::integral_constant<int, LOG2N>) for a supported size, `none` for any other: the one place that turns a run-time log2n into a template argument
+template <class R, class F>
+R for_log2n(int log2n, R none, F f)
+{
+    switch (log2n) {
+#define PV_CASE(L) case L: return f(std::integral_constant<int, L>{});
+    PV_CASE(8) PV_CASE(9) PV_CASE(10) PV_CASE(11) PV_CASE(12) PV_CASE(13)
+#undef PV_CASE
+    default: return none;
+    }
+}
 
 template <int LOG2N>
 struct SC {
@@ -62,6 +74,20 @@ struct MixSrc {
         return u;
     }
 };
+
+template <bool LINK>
+struct GroupSrc { using type = Src; };
+template <>
+struct GroupSrc<true> { using type = MixSrc; };
+
+// the source the phase path of a group reads: the slot's own stream, or the mix of the group's G slots starting at slot c0
+template <bool LINK>
+__device__ __forceinline__ typename GroupSrc<LINK>::type group_src(const PvStretchParams &p, int c0, int G, long hl)
+{
+    const float *sg = p.state_in + (long)c0 * p.state_stride;
+    if constexpr (LINK) return MixSrc{sg, p.in + (long)c0 * p.in_stride, hl, p.state_stride, p.in_stride, G};
+    else return Src{sg, p.in + (long)c0 * p.in_stride, hl};
+}
 
 // Where frames sit in the stream.  end(n) = S[n], the input consumed by frames 0 .. n-1; frame m's window starts at S[m + 1] - ha (the newest N samples
 // once its hop is in: hist is N - ha long) and its hop is S[m + 1] - S[m].  Wave-uniform: the table reads are scalar loads.

@@ -1,7 +1,7 @@
 """CPU checks of the transient surface: the header declares and the library exports pv_transient_process / _device, pv_onset_strength / _device,
 pv_transient_plan, pv_onsets_from_strength and the two chain-layout test hooks with the argument types the ctypes binding gives them, the ABI stays 6, the
-C planner and onset rule agree exactly with the numpy ones (tests/transient_model.py), no new kernel instance spills a VGPR or uses scratch, the
-instances that existed keep the resources of the commit before this feature, and examples/pv_transient.c builds as pedantic C99 (and, on a GPU, runs)."""
+C planner and onset rule agree exactly with the numpy ones (tests/transient_model.py), and examples/pv_transient.c builds as pedantic C99 (and, on a
+GPU, runs).  (The kernels' registers: tests/test_stretch_resources.py.)"""
 import ctypes as C
 import json
 import os
@@ -16,7 +16,6 @@ import transient_model as TM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "phaze_amd.h")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 SURFACE = {"pv_transient_process": 11, "pv_transient_process_device": 11, "pv_onset_strength": 7, "pv_onset_strength_device": 7, "pv_transient_plan": 12,
            "pv_onsets_from_strength": 7, "pv_transient_chain_layout": 5, "pv_onset_chain_layout": 4}
 
@@ -129,103 +128,6 @@ def test_c_onset_rule_equals_the_numpy_rule():
     assert phaze_amd.onsets_from_strength(np.zeros(0, np.int32), 1024, 256).size == 0
     with pytest.raises(ValueError):
         phaze_amd.onsets_from_strength([1, 2], 1024, 256, 0.0)
-
-
-# ---- kernel resources -----------------------------------------------------------------------------------------------------------------------
-
-FIELDS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "SGPRs Spill", "VGPRs Spill", "LDS Size"]
-# the instances of pv_stretch_kernels.hip and pv_link_kernels.hip as the commit before this feature compiles them (hipcc -O3 --offload-arch=gfx950,
-# -Rpass-analysis=kernel-resource-usage on a build of that commit), in the order of FIELDS
-PARENT = {
-    "_ZN12_GLOBAL__N_115pv_stretch_scanE15PvStretchParamsi": (33, 17, 0, 0, 8, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi8ELb1EEEv15PvStretchParams": (70, 76, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi8ELb1EEEv15PvStretchParams": (106, 96, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi8ELb0EEEv15PvStretchParams": (66, 80, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi8ELb0EEEv15PvStretchParams": (101, 100, 0, 0, 4, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi9ELb1EEEv15PvStretchParams": (78, 76, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi9ELb1EEEv15PvStretchParams": (106, 99, 0, 0, 4, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi9ELb0EEEv15PvStretchParams": (74, 80, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi9ELb0EEEv15PvStretchParams": (102, 102, 0, 0, 4, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi10ELb1EEEv15PvStretchParams": (76, 84, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi10ELb1EEEv15PvStretchParams": (106, 107, 0, 0, 4, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi10ELb0EEEv15PvStretchParams": (84, 82, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi10ELb0EEEv15PvStretchParams": (106, 107, 0, 0, 4, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi11ELb1EEEv15PvStretchParams": (70, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi11ELb1EEEv15PvStretchParams": (106, 115, 0, 0, 4, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi11ELb0EEEv15PvStretchParams": (74, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi11ELb0EEEv15PvStretchParams": (106, 121, 0, 0, 4, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi12ELb1EEEv15PvStretchParams": (66, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi12ELb1EEEv15PvStretchParams": (106, 140, 0, 0, 3, 2, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi12ELb0EEEv15PvStretchParams": (70, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi12ELb0EEEv15PvStretchParams": (106, 145, 0, 0, 3, 13, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi13ELb1EEEv15PvStretchParams": (66, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi13ELb1EEEv15PvStretchParams": (106, 243, 0, 0, 2, 16, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_aILi13ELb0EEEv15PvStretchParams": (70, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_117pv_stretch_pass_bILi13ELb0EEEv15PvStretchParams": (106, 247, 0, 0, 2, 20, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi8ELb1EEEv15PvStretchParamsi": (90, 76, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi8ELb1EEEv15PvStretchParamsi": (106, 99, 0, 0, 4, 19, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi8ELb0EEEv15PvStretchParamsi": (86, 80, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi8ELb0EEEv15PvStretchParamsi": (106, 105, 0, 0, 4, 11, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi9ELb1EEEv15PvStretchParamsi": (98, 76, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi9ELb1EEEv15PvStretchParamsi": (106, 100, 0, 0, 4, 8, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi9ELb0EEEv15PvStretchParamsi": (96, 80, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi9ELb0EEEv15PvStretchParamsi": (106, 107, 0, 0, 4, 6, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi10ELb1EEEv15PvStretchParamsi": (96, 78, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi10ELb1EEEv15PvStretchParamsi": (106, 109, 0, 0, 4, 18, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi10ELb0EEEv15PvStretchParamsi": (98, 78, 0, 0, 6, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi10ELb0EEEv15PvStretchParamsi": (106, 113, 0, 0, 4, 18, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi11ELb1EEEv15PvStretchParamsi": (88, 84, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi11ELb1EEEv15PvStretchParamsi": (106, 119, 0, 0, 4, 23, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi11ELb0EEEv15PvStretchParamsi": (86, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi11ELb0EEEv15PvStretchParamsi": (106, 121, 0, 0, 4, 25, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi12ELb1EEEv15PvStretchParamsi": (84, 84, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi12ELb1EEEv15PvStretchParamsi": (106, 140, 0, 0, 3, 26, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi12ELb0EEEv15PvStretchParamsi": (82, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi12ELb0EEEv15PvStretchParamsi": (106, 145, 0, 0, 3, 28, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi13ELb1EEEv15PvStretchParamsi": (84, 84, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi13ELb1EEEv15PvStretchParamsi": (106, 239, 0, 0, 2, 33, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_aILi13ELb0EEEv15PvStretchParamsi": (82, 86, 0, 0, 5, 0, 0, 0),
-    "_ZN12_GLOBAL__N_114pv_link_pass_bILi13ELb0EEEv15PvStretchParamsi": (106, 243, 0, 0, 2, 34, 0, 0),
-}
-
-
-def _resources(source):
-    src = os.path.join(ROOT, "phaze_amd", "csrc")
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                          "-o", os.devnull, source], cwd=src, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_transient_instances_keep_their_registers():
-    """Reset pass A and pass B for N = 256 .. 8192, unlinked and linked, the reset scan and the onset-strength kernel at six sizes: no VGPR spill, no
-    scratch, no AGPRs, <= 256 VGPRs.  Reset pass B at N = 8192 holds 243 (unlinked) / 245 (linked) VGPRs; the strength kernel 48 .. 62."""
-    k = _resources("stretch/pv_transient_kernels.hip")
-    assert sum("pv_reset_pass_a" in n for n in k) == 12 and sum("pv_reset_pass_b" in n for n in k) == 12
-    assert sum("pv_reset_scan" in n for n in k) == 1 and sum("pv_onset_strength_kernel" in n for n in k) == 6 and len(k) == 31, sorted(k)
-    for n, v in k.items():
-        assert v["VGPRs Spill"] == 0 and v["ScratchSize"] == 0 and v["AGPRs"] == 0 and v["VGPRs"] <= 256, (n, v)
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-@pytest.mark.parametrize("source", ["stretch/pv_stretch_kernels.hip", "stretch/pv_link_kernels.hip"])
-def test_existing_instances_keep_the_parents_resources(source):
-    k = _resources(source)
-    mine = {n: v for n, v in PARENT.items() if ("pv_link_" in n) == ("link" in source)}
-    assert set(k) == set(mine), sorted(set(k) ^ set(mine))
-    for n, v in k.items():
-        assert tuple(v[f] for f in FIELDS) == mine[n], (n, v, mine[n])
 
 
 # ---- the example ------------------------------------------------------------------------------------------------------------------------------

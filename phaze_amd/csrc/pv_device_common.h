@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "pv_signal.h"
 #include "pv_mul_rounded.h"
+#include "pv_pk_math.h"
 
 // Measured on gfx950 (tools/lds_microbench.hip): ds_read2_b64 / ds_read2st64_b64 / ds_read2_b32 occupy the LDS pipe for 8 cycles, twice
 // the cost of the two single reads they replace (2 + 2); ds_write2_b64 is neutral.  The SI load/store optimizer forms them wherever
@@ -121,7 +122,52 @@ __device__ __forceinline__ float2 rotate_route(unsigned route, float2 v, const f
     const float2 w = tw32[ridx & ((1u << LOG2N_) - 1u)];                  // masked: NOROUTE carries ridx = 0xFFFF
     return float2{__fmaf_rn(v.x, w.x, __fmul_rn(v.y, w.y)), __fmaf_rn(v.y, w.x, -__fmul_rn(v.x, w.y))};
 }
+// v * exp(+2 pi j ridx / N) in doubles (rotate_route's fp64 twin: the reference-width flavours)
+template <int R_, int LOG2N_>
+__device__ __forceinline__ double2 rotate_route_d(unsigned route, double2 v, const double2 *__restrict__ tw64)
+{
+    const unsigned ridx = (route >> 16) & ((1u << LOG2N_) - 1u);
+    if (R_ == 4) { const unsigned q = ridx >> (LOG2N_ - 2); return q == 0 ? v : q == 1 ? double2{-v.y, v.x} : q == 2 ? double2{-v.x, -v.y} : double2{v.y, -v.x}; }   // j^q exactly
+    const double2 w = tw64[ridx];                                          // exp(-2 pi j ridx / N): v * conj(w), roundings spelled out (see rotate_route)
+    return double2{__fma_rn(v.x, w.x, __dmul_rn(v.y, w.y)), __fma_rn(v.y, w.x, -__dmul_rn(v.x, w.y))};
+}
 
+// o * W_32^r = o * exp(-2 pi j r / 32), r = 0..7 (compile-time), fp64: the wave-uniform (row) part of the split-pass twiddle of the 2048- and 8192-point frames
+__device__ __forceinline__ double2 mul_w32(double2 o, int r)
+{
+    constexpr double c[9] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440,
+                             0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785, 0.0};
+    if (r == 0) return o;
+    return cmul(o, double2{c[r], -c[8 - r]});      // sin(2 pi r / 32) = cos(2 pi (8 - r) / 32)
+}
+
+// o * exp(+2 pi j r / 32), r = 0..7 (compile-time), packed fp32: the same row part in the c2r twiddle
+__device__ __forceinline__ pk::c32 mul_w32_inv_pk(pk::c32 o, int r)
+{
+    constexpr float c[9] = {1.0f, 0.98078528040323044913f, 0.92387953251128675613f, 0.83146961230254523708f, 0.70710678118654752440f,
+                            0.55557023301960222474f, 0.38268343236508977173f, 0.19509032201612826785f, 0.0f};
+    if (r == 0) return o;
+    return pk::cmul(o, pk::c32{c[r], c[8 - r]});
+}
+// o * exp(+2 pi j r / 16), r = 0..3 (compile-time): the wave-uniform part of the c2r twiddle of the 1024-, 4096- and (eight-element) 8192-point frames, packed
+__device__ __forceinline__ pk::c32 mul_w16_inv_pk(pk::c32 o, int r)
+{
+    const float c = 0.92387953251128675613f, sn = 0.38268343236508977173f, h = 0.70710678118654752440f;
+    switch (r) {
+    case 0: return o;
+    case 1: return pk::cmul(o, pk::c32{c, sn});
+    case 2: return pk::mul(pk::add_j(o, o), pk::c32{h, h});
+    default: return pk::cmul(o, pk::c32{sn, c});
+    }
+}
+
+// base-4 digit reversal over nd digits (fft.js's input order of a radix-4 DIT, bundle:468-508)
+__device__ __forceinline__ int digitrev4(int v, int nd)
+{
+    if (nd == 0) return 0;
+    const unsigned r = __brev((unsigned)v) >> (32 - 2 * nd);
+    return (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
+}
 
 // Register <-> lane transpose WITHOUT LDS: exchanges the register index (8 registers) with the HIGH three lane bits, one bit per stage (see
 // pv_wave_fft.h, "transpose 1 of the wave FFTs in registers"); used by the wave FFTs and by transpose 2 of the 8192-point workgroup FFT.
@@ -160,6 +206,80 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- claim rounds of a workgroup: the colliding scatter of f < 1 frames (pv:169-170; pv_wave_kernel.hip has the story and the one-wave form) ----
+// The loop condition is reduced over the workgroup, and -- because several waves race for a claim word here -- a source posts its bin
+// with an LDS atomic MIN: the smallest pending source bin wins the round, so every target accumulates its contributions in ascending source order
+// (the order of the reference's loops, pv:122,146) whatever the timing of the waves; results are reproducible bit for bit for every f.
+// CLAIM[0..H) must be all-ones on entry and is all-ones on exit.
+template <int NS, int H_, typename V2>
+__device__ __forceinline__ void claim_rounds_wg(const unsigned (&rt)[NS], const V2 (&ys)[NS], const int (&id)[NS], V2 *Y, unsigned *CLAIM)
+{
+    unsigned pend = 0;
+    unsigned tg[NS];
+#pragma unroll
+    for (int r = 0; r < NS; r++) {
+        const unsigned t = rt[r] & 0xFFFFu;
+        const bool ok = t < (unsigned)H_;                                  // valid route <=> target field < H
+        pend |= ok ? (1u << r) : 0u;
+        tg[r] = ok ? t : 0u;
+    }
+    while (__syncthreads_or(pend != 0u)) {
+#pragma unroll
+        for (int r = 0; r < NS; r++) if (pend & (1u << r)) atomicMin(&CLAIM[tg[r]], (unsigned)id[r]);
+        __syncthreads();
+        unsigned c[NS];
+        V2 o[NS];
+#pragma unroll
+        for (int r = 0; r < NS; r++) c[r] = CLAIM[tg[r]];                   // independent reads first, then the winners' stores (see pv_wave_kernel.hip)
+#pragma unroll
+        for (int r = 0; r < NS; r++) o[r] = Y[tg[r]];
+#pragma unroll
+        for (int r = 0; r < NS; r++) {
+            if ((pend & (1u << r)) && c[r] == (unsigned)id[r]) {
+                Y[tg[r]] = V2{o[r].x + ys[r].x, o[r].y + ys[r].y};
+                CLAIM[tg[r]] = 0xFFFFFFFFu;                                // only the winner touches the word; losers re-post after the barrier
+                pend &= ~(1u << r);
+            }
+        }
+    }
+}
+
+// ---- the poll of the resident (streaming) instances: wait for the next quantum's control word in pinned host memory ----
+// The word carries the whole quantum -- sequence number (low 16 bits, never 0), channel count (7 bits), ping-pong half (1 bit), timeCursor / hop mod R
+// (8 bits) -- so that a successful poll needs no second round trip over PCIe before the input can be requested.  Returns the word behind a system-scope
+// acquire fence (what the host wrote before the word), or 0 when the host asks the waves to leave (ctl[4]) or after idle_ticks (~50 ms) without work:
+// the host relaunches on demand, a resident wave must never outlive its user.  0 is free for that because a sequence number is never 0 (pv_capi.hip
+// skips it when the counter wraps), so no word the host posts is 0; a caller leaves on 0 whichever way it came about.
+__device__ __forceinline__ unsigned resident_poll_word(const unsigned *word_at, const unsigned *ctl, unsigned last_seq, unsigned idle_ticks)
+{
+    unsigned word;
+    const unsigned long long idle0 = wall_clock64();
+    for (;;) {
+        word = __hip_atomic_load(word_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((word & 0xFFFFu) != (last_seq & 0xFFFFu)) break;
+        if (__hip_atomic_load(ctl + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || wall_clock64() - idle0 > (unsigned long long)idle_ticks) return 0u;
+        __builtin_amdgcn_s_sleep(2);
+    }
+    return word;
+}
+// one wave per channel slot (N = 1024): every wave polls ctl[0]
+__device__ __forceinline__ unsigned resident_poll_wave(const unsigned *ctl, unsigned last_seq, unsigned idle_ticks)
+{
+    const unsigned word = resident_poll_word(ctl, ctl, last_seq, idle_ticks);
+    if (word != 0u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    return word;
+}
+// one workgroup per channel slot: thread 0 polls the slot's OWN word ctl[16 + ch] and hands it to the others through `bc`, an LDS word that is not live here
+__device__ __forceinline__ unsigned resident_poll_wg(const unsigned *ctl, int ch, unsigned last_seq, unsigned idle_ticks, unsigned *bc, int t)
+{
+    if (t == 0) bc[0] = resident_poll_word(ctl + 16 + ch, ctl, last_seq, idle_ticks);
+    __syncthreads();
+    const unsigned word = bc[0];
+    __syncthreads();
+    if (word != 0u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    return word;
 }
 
 }  // namespace

@@ -68,6 +68,25 @@ inline hipError_t pv_set_dynamic_lds_once(std::atomic<bool> (&done)[16], const v
     return e;
 }
 
+// One launch of one kernel instance, shared by the launchers of the frame kernels: the instance's dynamic-LDS limit is raised once per device (lds_limit bytes when a
+// launch may use less than a later one of the same instance), then the launch and its error.  KERNEL is a template argument so that every instance has its own flags.
+template <void (*KERNEL)(const PvKernelParams)>
+inline hipError_t pv_launch_instance(dim3 grid, dim3 block, size_t lds, hipStream_t st, const PvKernelParams &q, size_t lds_limit = 0)
+{
+    static std::atomic<bool> attr_done[16];
+    const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(KERNEL), (int)(lds_limit ? lds_limit : lds));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, q);
+    return hipGetLastError();
+}
+// The parameters of a resident (streaming) launch: one frame chain per channel slot and one hop per quantum; slots beyond the handle's leave at once.
+inline PvKernelParams pv_resident_params(const PvKernelParams &p, int nslots)
+{
+    PvKernelParams q = p;
+    q.nchunks = 1; q.nch = nslots; q.nhops = 1; q.frames_per_chunk = 1;
+    return q;
+}
+
 int pv_kernel_threads(int log2n);
 size_t pv_kernel_lds_bytes(int log2n, int hop);
 size_t pv_kernel_gscratch_bytes(int log2n, int hop);      // per workgroup; 0 for N <= 8192 (everything in LDS)

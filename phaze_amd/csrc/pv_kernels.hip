@@ -19,8 +19,7 @@
 #include <type_traits>
 
 #include "pv_kernels.h"
-#include "pv_signal.h"
-#include "pv_mul_rounded.h"
+#include "pv_device_common.h"
 
 namespace {
 
@@ -31,22 +30,13 @@ template <typename T> struct vec2;
 template <> struct vec2<float> { using type = float2; };
 template <> struct vec2<double> { using type = double2; };
 
-template <typename T2> __device__ __forceinline__ T2 cadd(T2 a, T2 b) { return T2{a.x + b.x, a.y + b.y}; }
-template <typename T2> __device__ __forceinline__ T2 csub(T2 a, T2 b) { return T2{a.x - b.x, a.y - b.y}; }
-template <typename T2> __device__ __forceinline__ T2 cmul(T2 a, T2 b) { return T2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-template <typename T2> __device__ __forceinline__ T2 cconj(T2 a) { return T2{a.x, -a.y}; }
+// cadd, csub, cmul, cconj: pv_device_common.h
 // multiply by -j (forward) / +j (inverse)
 template <bool INV, typename T2> __device__ __forceinline__ T2 cmul_mj(T2 a) { return INV ? T2{-a.y, a.x} : T2{a.y, -a.x}; }
 
 // mul_rounded (a * b rounded to fp32 as an operation of its own, pv:55,67): pv_mul_rounded.h, shared with the register kernels
 __device__ __forceinline__ int bitrev(int v, int bits) { return bits == 0 ? 0 : (int)(__brev((unsigned)v) >> (32 - bits)); }
-// base-4 digit reversal over nd digits
-__device__ __forceinline__ int digitrev4(int v, int nd)
-{
-    if (nd == 0) return 0;
-    unsigned r = __brev((unsigned)v) >> (32 - 2 * nd);
-    return (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
-}
+// digitrev4 (base-4 digit reversal): pv_device_common.h
 
 // ------------------------------------------------------------------------------------------------
 // In-place radix-2^2 DIT FFT of MP = 2^LOG2M complex points held in LDS in BIT-REVERSED order;
@@ -464,15 +454,8 @@ __global__ __launch_bounds__(THREADS) void pv_chain_kernel(const PvKernelParams 
 template <int LOG2N, int THREADS, int GM = 0>
 hipError_t launch_one(const PvKernelParams &p, int nch, int nchunks, size_t lds, hipStream_t st)
 {
-    static std::atomic<bool> attr_done[16];
-    auto k = pv_chain_kernel<LOG2N, THREADS, GM>;
     if (GM && (p.gscratch == nullptr || p.gscratch_stride < pv_kernel_gscratch_bytes(LOG2N, p.hop))) return hipErrorInvalidValue;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(k), 160 * 1024 - 512);   // __syncthreads_or keeps a few static bytes
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(nchunks, nch, 1), dim3(THREADS, 1, 1), lds, st, p);
-    return hipGetLastError();
+    return pv_launch_instance<pv_chain_kernel<LOG2N, THREADS, GM>>(dim3(nchunks, nch, 1), dim3(THREADS, 1, 1), lds, st, p, 160 * 1024 - 512);   // __syncthreads_or keeps a few static bytes
 }
 
 }  // namespace

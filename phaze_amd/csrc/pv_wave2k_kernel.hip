@@ -71,22 +71,6 @@ constexpr int N2 = 2048, M2 = 1024, H2 = 1025;
 //   P(l + 64 r) = pl + 80 r, pl = l + 4 (l >> 4);   P(1024 - l - 64 r) = 1280 - ql - 80 r, ql = l + 4 ((l + 15) >> 4);   P(512) = 640, P(1024) = 1280
 constexpr int MAG0 = 8;                           // magnitudes start 8 words in: bins -2, -1 of lane 0's window stay inside the region
 
-// o * W_32^r = o * exp(-2 pi j r / 32), r = 0..7 (compile-time), fp64: the wave-uniform part of the split-pass twiddle
-__device__ __forceinline__ double2 mul_w32(double2 o, int r)
-{
-    constexpr double c[8] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440,
-                             0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785};
-    if (r == 0) return o;
-    return cmul(o, double2{c[r], -c[8 - r]});      // sin(2 pi r / 32) = cos(2 pi (8 - r) / 32)
-}
-// o * exp(+2 pi j r / 32), packed fp32 (c2r twiddle)
-__device__ __forceinline__ pk::c32 mul_w32_inv_pk(pk::c32 o, int r)
-{
-    constexpr float c[9] = {1.0f, 0.98078528040323044913f, 0.92387953251128675613f, 0.83146961230254523708f, 0.70710678118654752440f,
-                            0.55557023301960222474f, 0.38268343236508977173f, 0.19509032201612826785f, 0.0f};
-    if (r == 0) return o;
-    return pk::cmul(o, pk::c32{c[r], c[8 - r]});
-}
 // o * exp(+2 pi j r / 16), r = 0..7, packed fp32 (first stage of the decimation-in-frequency inverse)
 __device__ __forceinline__ pk::c32 mul_w16_inv_pk8(pk::c32 o, int r)
 {
@@ -171,12 +155,6 @@ __device__ __forceinline__ float2 rotate2k(unsigned route, float2 v, const float
     return cmul(v, ROT[(route >> 23) & 15u]);                              // bits 23..26 of the route = top four bits of the rotation index
 }
 
-__device__ __forceinline__ int digitrev4_2k(int v, int nd)
-{
-    const unsigned r = __brev((unsigned)v) >> (32 - 2 * nd);
-    return (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
-}
-
 // Rare path (f < 1 frames whose last region reads beyond position N/2 + N/8): what fft.js's in-place real DIT leaves at positions
 // N/2+1 .. N-1, one quarter of the buffer at a time (quarter 2 = sub-FFT of xw[4n+2], positions 1024..1535; quarter 3 = xw[4n+3], 1536..2047),
 // by re-running the reference's stage structure on that quarter in fp32 (log2 N odd: radix-2 base blocks, bundle:447-463, then the radix-4
@@ -198,7 +176,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_2k(cons
 #pragma unroll
         for (int i = 0; i < 4; i++) {                                      // QN / 2 = 256 radix-2 blocks per quarter; input index = base-4 digit reversal of the block
             const int lb = l + 64 * i, blk = base / 2 + lb;
-            const int off = digitrev4_2k(blk, (LOG2N - 1) / 2);
+            const int off = digitrev4(blk, (LOG2N - 1) / 2);
             const float a = mul_rounded(src.at(s0 + off), hann[off]), b = mul_rounded(src.at(s0 + off + N / 2), hann[off + N / 2]);
             Q[2 * lb] = float2{a + b, 0.f};
             Q[2 * lb + 1] = float2{a - b, 0.f};
@@ -1176,14 +1154,6 @@ resident_top:
 template <int HOPQ, bool AUX>
 hipError_t launch2k(const PvKernelParams &p, int nch, int nchunks, hipStream_t st)
 {
-    static std::atomic<bool> attr_done[16], attr_done_f[16];
-    // the product's instances run the forward transform in fp32 first (F32; pv_guard.h); with p.fwd64 != 0 (PV_FLAG_FP64_FORWARD) and in the tap instance every frame runs the fp64 one
-    const bool f32 = !AUX && !p.fwd64;
-    auto k = f32 ? pv_wave2k_kernel<HOPQ, AUX, false, !AUX> : pv_wave2k_kernel<HOPQ, AUX, false, false>;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(f32 ? attr_done_f : attr_done, reinterpret_cast<const void *>(k), (int)pv_wave2k_lds_bytes());
-        if (e != hipSuccess) return e;
-    }
     PvKernelParams q = p;
     q.nchunks = nchunks;
     q.nch = nch;
@@ -1197,25 +1167,22 @@ hipError_t launch2k(const PvKernelParams &p, int nch, int nchunks, hipStream_t s
     long w = (chains + cus - 1) / cus;
     if (w < PV_W2K_WMIN) w = PV_W2K_WMIN;
     if (w > WAVES2) w = WAVES2;
-    hipLaunchKernelGGL(k, dim3((unsigned)((chains + w - 1) / w), 1, 1), dim3(64 * (unsigned)w, 1, 1), T2_BYTES + (size_t)w * WAVE2_LDS, st, q);
-    return hipGetLastError();
+    const dim3 grid((unsigned)((chains + w - 1) / w), 1, 1), block(64 * (unsigned)w, 1, 1);
+    const size_t lds = T2_BYTES + (size_t)w * WAVE2_LDS;
+    // the product's instances run the forward transform in fp32 first (F32; pv_guard.h); with p.fwd64 != 0 (PV_FLAG_FP64_FORWARD) and in the tap instance every frame runs the fp64 one
+    return (!AUX && !p.fwd64) ? pv_launch_instance<pv_wave2k_kernel<HOPQ, AUX, false, !AUX>>(grid, block, lds, st, q, pv_wave2k_lds_bytes())
+                              : pv_launch_instance<pv_wave2k_kernel<HOPQ, AUX, false, false>>(grid, block, lds, st, q, pv_wave2k_lds_bytes());
 }
 
 template <int HOPQ>
 hipError_t launch2k_resident(const PvKernelParams &p, int nslots, hipStream_t st)
 {
-    static std::atomic<bool> attr_done[16], attr_done_f[16];
-    const bool f32 = !p.fwd64;
-    auto k = f32 ? pv_wave2k_kernel<HOPQ, false, true, true> : pv_wave2k_kernel<HOPQ, false, true, false>;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(f32 ? attr_done_f : attr_done, reinterpret_cast<const void *>(k), (int)pv_wave2k_lds_bytes());
-        if (e != hipSuccess) return e;
-    }
-    PvKernelParams q = p;
-    q.nchunks = 1; q.nch = nslots; q.nhops = 1; q.frames_per_chunk = 1;
     constexpr int w = 2;                                                   // two channel slots per workgroup: the slots spread over the CUs
-    hipLaunchKernelGGL(k, dim3((unsigned)((nslots + w - 1) / w), 1, 1), dim3(64 * w, 1, 1), T2_BYTES + (size_t)w * WAVE2_LDS, st, q);
-    return hipGetLastError();
+    const dim3 grid((unsigned)((nslots + w - 1) / w), 1, 1), block(64 * w, 1, 1);
+    const size_t lds = T2_BYTES + (size_t)w * WAVE2_LDS;
+    const PvKernelParams q = pv_resident_params(p, nslots);
+    return !p.fwd64 ? pv_launch_instance<pv_wave2k_kernel<HOPQ, false, true, true>>(grid, block, lds, st, q, pv_wave2k_lds_bytes())
+                    : pv_launch_instance<pv_wave2k_kernel<HOPQ, false, true, false>>(grid, block, lds, st, q, pv_wave2k_lds_bytes());
 }
 
 }  // namespace

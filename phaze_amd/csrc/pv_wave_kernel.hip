@@ -30,6 +30,7 @@
 #include "pv_kernels.h"
 #include "pv_device_common.h"
 #include "pv_pk_math.h"
+#include "pv_residue.h"
 #include "pv_wave_fft.h"
 #include "pv_guard.h"
 
@@ -71,18 +72,6 @@ __device__ __forceinline__ float2 tw1f_at(int k, int l)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     return reinterpret_cast<const float2 *>(smem_all + TAB_TW1F)[2 * ((k >> 1) * 64 + l) + (k & 1)];
-}
-
-// o * exp(+2 pi j r / 16), r = 0..3 (compile-time): the wave-uniform part of the c2r twiddle, packed
-__device__ __forceinline__ pk::c32 mul_w16_inv_pk(pk::c32 o, int r)
-{
-    const float c = 0.92387953251128675613f, sn = 0.38268343236508977173f, h = 0.70710678118654752440f;
-    switch (r) {
-    case 0: return o;
-    case 1: return pk::cmul(o, pk::c32{c, sn});
-    case 2: return pk::mul(pk::add_j(o, o), pk::c32{h, h});
-    default: return pk::cmul(o, pk::c32{sn, c});
-    }
 }
 
 
@@ -322,14 +311,6 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_1024(co
 
 
 // ---- fp64 flavour (PV_FP64_FLAVOUR): the colliding scatter and the above-Nyquist residue in doubles, on a plain array Y[513] ----
-__device__ __forceinline__ double2 rotate_route_d(int r_, unsigned route, double2 v, const double2 *__restrict__ tw64)
-{
-    const unsigned ridx = (route >> 16) & 1023u;
-    if (r_ == 4) { const unsigned q = ridx >> 8; return q == 0 ? v : q == 1 ? double2{-v.y, v.x} : q == 2 ? double2{-v.x, -v.y} : double2{v.y, -v.x}; }   // j^q exactly
-    const double2 w = tw64[ridx];                                          // exp(-2 pi j ridx / N): v * conj(w), roundings spelled out (see rotate_route)
-    return double2{__fma_rn(v.x, w.x, __dmul_rn(v.y, w.y)), __fma_rn(v.y, w.x, -__dmul_rn(v.x, w.y))};
-}
-
 template <int NS, bool YZERO>
 __device__ __forceinline__ void claim_rounds_d(const unsigned (&rt)[NS], const double2 (&ys)[NS], const int (&id)[NS], double2 *Y, unsigned short *CLAIM)
 {
@@ -362,72 +343,36 @@ __device__ __forceinline__ void claim_rounds_d(const unsigned (&rt)[NS], const d
     }
 }
 
-// residue_scatter_1024 in doubles: the reference's stage structure (bundle:306-442,468-508) re-run on one quarter at a time, twiddles from the
-// forward FFT's fp64 table (row 2m of W_512^{l k} = W_1024^{4 m l}), the window product rounded to fp32 as the reference's Float32Array does (pv:55).
+// residue_scatter_1024 in doubles: the reference's stage structure re-run on one quarter at a time, twiddles from the forward FFT's fp64 table
+// (row 2m of W_512^{l k} = W_1024^{4 m l}), the window product rounded to fp32 as the reference's Float32Array does (pv:55).
+template <int R_>
+struct Residue1024D {
+    using V2 = double2;
+    static constexpr int LOG2N = 10, T = 64, ID0 = 0;
+    static constexpr bool UNROLL_STAGES = true;
+    WaveSrc src; long s0; const float *hann; const double2 *tw64;
+    double2 *Y; unsigned short *CLAIM; double2 *Qp; const double2 *TW1;
+    __device__ __forceinline__ double2 *Q() const { return Qp; }
+    __device__ __forceinline__ void sync() const { wave_sync(); }
+    __device__ __forceinline__ double sample(int, int smp) const { return (double)__fmul_rn(src.at(s0 + smp), hann[smp]); }
+    __device__ __forceinline__ void twiddles(int i, int, int tws, double2 &w1, double2 &w2, double2 &w3) const
+    {
+        const int c = i << (tws - 2);
+        w1 = TW1[2 * 64 + c]; w2 = TW1[4 * 64 + c]; w3 = TW1[6 * 64 + c];
+    }
+    __device__ __forceinline__ double2 rotate(unsigned route, double2 v) const { return rotate_route_d<R_, 10>(route, v, tw64); }
+    __device__ __forceinline__ void add(const unsigned (&rt)[4], const double2 (&ys)[4], const int (&id)[4]) const { claim_rounds_d<4, false>(rt, ys, id, Y, CLAIM); }
+};
 template <int R_>
 __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_1024_d(const float *in, const float *hist, int hist_len, long s0, const float *__restrict__ hann,
                                                                                const double2 *__restrict__ tw64, unsigned wave_off, int l, int upper_end, int up_delta,
                                                                                unsigned up_ridx, double *dbg_X)
 {
-    constexpr int N = 1024, H = 513;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    double2 *Y = reinterpret_cast<double2 *>(smem_all + wave_off + OFF_Y);
-    unsigned short *CLAIM = reinterpret_cast<unsigned short *>(smem_all + wave_off + F64_ROUTE);
-    double2 *Q = reinterpret_cast<double2 *>(smem_all + wave_off + F64_Q);
-    const double2 *TW1 = reinterpret_cast<const double2 *>(smem_all + TAB_TW1);
-    const WaveSrc src{in, hist, hist_len, false};
-    for (int base = N / 2; base < N && base < upper_end; base += N / 4) {
-        {
-            const int t = base / 4 + l;
-            const unsigned rv = __brev((unsigned)t) >> (32 - 8);
-            const int off = (int)(((rv & 0x55555555u) << 1) | ((rv >> 1) & 0x55555555u));
-            const double a = (double)__fmul_rn(src.at(s0 + off), hann[off]), b = (double)__fmul_rn(src.at(s0 + off + N / 4), hann[off + N / 4]);
-            const double c = (double)__fmul_rn(src.at(s0 + off + N / 2), hann[off + N / 2]), d = (double)__fmul_rn(src.at(s0 + off + 3 * N / 4), hann[off + 3 * N / 4]);
-            const double t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
-            Q[4 * l] = double2{t0 + t2, 0.0};
-            Q[4 * l + 1] = double2{t1, -t3};
-            Q[4 * l + 2] = double2{t0 - t2, 0.0};
-            Q[4 * l + 3] = double2{t1, t3};
-        }
-        wave_sync();
-#pragma unroll
-        for (int log2m = 4; log2m <= 8; log2m += 2) {
-            const int q = (1 << log2m) >> 2, hq = q >> 1;
-            const int nblocks = 256 >> log2m, step = 256 >> log2m;
-            if (l < nblocks * (hq + 1)) {
-                int blk, i;
-                if (l < nblocks * hq) { blk = l / hq; i = l - blk * hq; } else { blk = l - nblocks * hq; i = hq; }
-                const int o = blk << log2m;
-                const double2 A = Q[o + i];
-                const double2 Bv = cmul(Q[o + q + i], TW1[2 * 64 + i * step]);
-                const double2 C = cmul(Q[o + 2 * q + i], TW1[4 * 64 + i * step]);
-                const double2 D = cmul(Q[o + 3 * q + i], TW1[6 * 64 + i * step]);
-                const double2 T0 = cadd(A, C), T1 = csub(A, C), T2 = cadd(Bv, D), T3 = csub(Bv, D);
-                Q[o + i] = cadd(T0, T2);
-                Q[o + q + i] = double2{T1.x + T3.y, T1.y - T3.x};
-                if (i == 0) {
-                    Q[o + 2 * q] = csub(T0, T2);
-                } else if (i != hq) {
-                    Q[o + q - i] = double2{T1.x - T3.y, -(T1.y + T3.x)};
-                    Q[o + 2 * q - i] = double2{T0.x - T2.x, -(T0.y - T2.y)};
-                }
-            }
-            wave_sync();
-        }
-        if (dbg_X)
-            for (int i = l; i < N / 4; i += 64) if (base + i >= H) { dbg_X[2 * (base + i)] = Q[i].x; dbg_X[2 * (base + i) + 1] = Q[i].y; }
-        unsigned rt[4];
-        double2 ys[4];
-        int id[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int b = base + l + 64 * j, tgt = b + up_delta;
-            rt[j] = (b >= H && b < upper_end && tgt >= 0 && tgt < H) ? ((up_ridx << 16) | (unsigned)tgt) : NOROUTE;
-            ys[j] = rotate_route_d(R_, rt[j], Q[l + 64 * j], tw64);
-            id[j] = b;
-        }
-        claim_rounds_d<4, false>(rt, ys, id, Y, CLAIM);
-    }
+    const Residue1024D<R_> k{WaveSrc{in, hist, hist_len, false}, s0, hann, tw64, reinterpret_cast<double2 *>(smem_all + wave_off + OFF_Y),
+                             reinterpret_cast<unsigned short *>(smem_all + wave_off + F64_ROUTE), reinterpret_cast<double2 *>(smem_all + wave_off + F64_Q),
+                             reinterpret_cast<const double2 *>(smem_all + TAB_TW1)};
+    residue_quarters(k, l, upper_end, up_delta, up_ridx, dbg_X);
 }
 
 // Shift table DSH[p] = Math.round(p * f) - p (pv:125,147) for every candidate peak bin, DROP where the reference skips the peak (pv:127-129).
@@ -721,18 +666,8 @@ __global__ __launch_bounds__(64 * (RESIDENT ? RES_WAVES : WAVES), RESIDENT ? 1 :
                                                                          // of the resident form's loop: a resident wave's quanta are ONE chain of a stream
 resident_top:
     if (RESIDENT) {
-        // ctl[0] carries the whole quantum in ONE word -- sequence number (low 16 bits, never 0), channel count (7 bits), ping-pong half (1 bit),
-        // timeCursor / hop mod R (8 bits) -- so that a successful poll needs no second round trip over PCIe before the input can be requested
-        unsigned word;
-        const unsigned long long idle0 = wall_clock64();
-        for (;;) {
-            word = __hip_atomic_load(p.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if ((word & 0xFFFFu) != (last_seq & 0xFFFFu)) break;
-            // leave when asked to, or after ~50 ms without work (the host relaunches on demand: a resident wave must never outlive its user)
-            if (__hip_atomic_load(p.ctl + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || wall_clock64() - idle0 > (unsigned long long)p.idle_ticks) return;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                    // system scope: what the host wrote before the word
+        const unsigned word = resident_poll_wave(p.ctl, last_seq, p.idle_ticks);      // the next quantum's control word (pv_device_common.h)
+        if (word == 0u) return;
         const unsigned seq = word & 0xFFFFu, nch_now = (word >> 16) & 0x7Fu, cur = (word >> 23) & 1u;
         t0_mod_n = (int)(((word >> 24) & 0xFFu) * HOP) & (N - 1);
         hist_in = p.hist2[cur]; hist_out = p.hist2[cur ^ 1u];
@@ -1240,10 +1175,10 @@ resident_top:
                 for (int r = 0; r < 4; r++) {
                     const unsigned ra = ROUTE[l + 64 * r], ta = ra & 0xFFFFu;
                     const unsigned rb = ROUTE[512 - l - 64 * r], tb = rb & 0xFFFFu;
-                    if (ta < (unsigned)H) Yd[ta] = rotate_route_d(R, ra, XAd[r], p.tw64);
-                    if (tb < (unsigned)H) Yd[tb] = rotate_route_d(R, rb, XBd[r], p.tw64);
+                    if (ta < (unsigned)H) Yd[ta] = rotate_route_d<R, 10>(ra, XAd[r], p.tw64);
+                    if (tb < (unsigned)H) Yd[tb] = rotate_route_d<R, 10>(rb, XBd[r], p.tw64);
                 }
-                if (l == 0) { const unsigned r256 = ROUTE[256], tg = r256 & 0xFFFFu; if (tg < (unsigned)H) Yd[tg] = rotate_route_d(R, r256, x256d, p.tw64); }
+                if (l == 0) { const unsigned r256 = ROUTE[256], tg = r256 & 0xFFFFu; if (tg < (unsigned)H) Yd[tg] = rotate_route_d<R, 10>(r256, x256d, p.tw64); }
             } else {
                 // f < 1 (and NaN): `+=` collisions (pv:169-170) resolved by claim rounds, then the sources above Nyquist (all owned by the last peak, pv:133)
                 // from the re-run stage structure -- this flavour has neither the pairwise scatter nor the closed form of the residue
@@ -1252,11 +1187,11 @@ resident_top:
                 int id[9];
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    id[r] = l + 64 * r; rc[r] = ROUTE[id[r]]; ys[r] = rotate_route_d(R, rc[r], XAd[r], p.tw64);
-                    id[4 + r] = 512 - l - 64 * r; rc[4 + r] = ROUTE[id[4 + r]]; ys[4 + r] = rotate_route_d(R, rc[4 + r], XBd[r], p.tw64);
+                    id[r] = l + 64 * r; rc[r] = ROUTE[id[r]]; ys[r] = rotate_route_d<R, 10>(rc[r], XAd[r], p.tw64);
+                    id[4 + r] = 512 - l - 64 * r; rc[4 + r] = ROUTE[id[4 + r]]; ys[4 + r] = rotate_route_d<R, 10>(rc[4 + r], XBd[r], p.tw64);
                 }
                 rc[8] = (l == 0) ? ROUTE[256] : NOROUTE;
-                ys[8] = rotate_route_d(R, rc[8], x256d, p.tw64);
+                ys[8] = rotate_route_d<R, 10>(rc[8], x256d, p.tw64);
                 id[8] = 256;
                 wave_sync();                                               // routes are in registers: the claim words may overwrite them
                 claim_rounds_d<9, true>(rc, ys, id, Yd, CLAIM);
@@ -1592,62 +1527,44 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void pv_classify_chains(const PvKer
 template <int S_ROWS, bool AUX>
 hipError_t launch_wave(const PvKernelParams &p, int nch, int nchunks, hipStream_t st, int spread, unsigned *list, unsigned *list_next)
 {
-    static std::atomic<bool> attr_done[16], attr_done_s[16];
-    static std::atomic<bool> attr_done_f[16], attr_done_g[16];
     // F32FWD: the product's instances take the peak decisions on an fp32 forward transform behind a guard band (F32; p.fwd64 = 0); with p.fwd64 != 0, in the tap
     // instance and in the reference-width flavour every frame runs the fp64 forward transform (the round-4 kernels, bit for bit)
     constexpr bool F32OK = !AUX && !FP64;
     const bool f32 = F32OK && !p.fwd64;
-    auto k = f32 ? pv_wave_kernel_1024<S_ROWS, AUX, false, false, F32OK> : pv_wave_kernel_1024<S_ROWS, AUX, false, false, false>;
-    auto ks = f32 ? pv_wave_kernel_1024<S_ROWS, false, false, true, F32OK> : pv_wave_kernel_1024<S_ROWS, false, false, true>;
-    {
-        hipError_t e = pv_set_dynamic_lds_once(f32 ? attr_done_g : attr_done, reinterpret_cast<const void *>(k), (int)pv_wave_lds_bytes());
-        if (e == hipSuccess && !AUX) e = pv_set_dynamic_lds_once(f32 ? attr_done_f : attr_done_s, reinterpret_cast<const void *>(ks), (int)pv_wave_lds_bytes());
-        if (e != hipSuccess) return e;
-    }
     PvKernelParams q = p;
     q.nchunks = nchunks;
     q.nch = nch;
     const long chains = (long)nch * nchunks;
     const dim3 grid((unsigned)((chains + WAVES - 1) / WAVES), 1, 1), block(64 * WAVES, 1, 1);
-    if (FP64 && !AUX) {                                                    // reference-width flavour: ONE instance (the SPREAD flow with its own colliding scatter)
-        hipLaunchKernelGGL(ks, grid, block, pv_wave_lds_bytes(), st, q);
-    } else if (AUX || spread == 0 || (spread < 0 && !list)) {              // one instance that handles every pitchFactor
-        hipLaunchKernelGGL(k, grid, block, pv_wave_lds_bytes(), st, q);
-    } else if (spread > 0) {
-        if (!AUX) hipLaunchKernelGGL(ks, grid, block, pv_wave_lds_bytes(), st, q);
-    } else {
-        // classify on the device, then both instances over the whole grid: a workgroup beyond its class's count leaves at once
-        if (!list_next) {                                                  // (a caller without a second list: the counters are zeroed here, one more operation per launch)
-            hipError_t e = hipMemsetAsync(list, 0, 2 * sizeof(unsigned), st);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(pv_classify_chains<S_ROWS>, dim3((unsigned)((chains + CLS_WAVES - 1) / CLS_WAVES), 1, 1), dim3(64 * CLS_WAVES, 1, 1), 0, st, q, list, list_next);
-        q.chain_count = list;
-        q.chain_list = list + 2;
-        if (!AUX) hipLaunchKernelGGL(ks, grid, block, pv_wave_lds_bytes(), st, q);
-        hipLaunchKernelGGL(k, grid, block, pv_wave_lds_bytes(), st, q);
+    const size_t lds = pv_wave_lds_bytes();
+    // k: the instance for every pitchFactor, ks: the SPREAD instance (f >= 1 on every frame); each in its fp32-first or its fp64 form.  An instance's LDS limit is
+    // raised when it is first launched, and a launch that fails ends the call: behind a failed ks() no k() is issued.
+    auto k = [&] { return f32 ? pv_launch_instance<pv_wave_kernel_1024<S_ROWS, AUX, false, false, F32OK>>(grid, block, lds, st, q)
+                              : pv_launch_instance<pv_wave_kernel_1024<S_ROWS, AUX, false, false, false>>(grid, block, lds, st, q); };
+    auto ks = [&] { return f32 ? pv_launch_instance<pv_wave_kernel_1024<S_ROWS, false, false, true, F32OK>>(grid, block, lds, st, q)
+                               : pv_launch_instance<pv_wave_kernel_1024<S_ROWS, false, false, true>>(grid, block, lds, st, q); };
+    if (FP64 && !AUX) return ks();                                         // reference-width flavour: ONE instance (the SPREAD flow with its own colliding scatter)
+    if (AUX || spread == 0 || (spread < 0 && !list)) return k();           // one instance that handles every pitchFactor
+    if (spread > 0) return ks();
+    // classify on the device, then both instances over the whole grid: a workgroup beyond its class's count leaves at once
+    if (!list_next) {                                                      // (a caller without a second list: the counters are zeroed here, one more operation per launch)
+        hipError_t e = hipMemsetAsync(list, 0, 2 * sizeof(unsigned), st);
+        if (e != hipSuccess) return e;
     }
-    return hipGetLastError();
+    hipLaunchKernelGGL(pv_classify_chains<S_ROWS>, dim3((unsigned)((chains + CLS_WAVES - 1) / CLS_WAVES), 1, 1), dim3(64 * CLS_WAVES, 1, 1), 0, st, q, list, list_next);
+    q.chain_count = list;
+    q.chain_list = list + 2;
+    const hipError_t e = ks();
+    return e != hipSuccess ? e : k();
 }
 
 template <int S_ROWS>
 hipError_t launch_wave_resident(const PvKernelParams &p, int nslots, hipStream_t st)
 {
-    static std::atomic<bool> attr_done[16], attr_done_f[16];
-    const bool f32 = !FP64 && !p.fwd64;
-    auto k = f32 ? pv_wave_kernel_1024<S_ROWS, false, true, false, !FP64> : pv_wave_kernel_1024<S_ROWS, false, true, false, false>;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(f32 ? attr_done_f : attr_done, reinterpret_cast<const void *>(k), (int)pv_wave_lds_bytes());
-        if (e != hipSuccess) return e;
-    }
-    PvKernelParams q = p;
-    q.nchunks = 1;
-    q.nch = nslots;                                                        // waves beyond the handle's channel slots leave at once
-    q.nhops = 1;
-    q.frames_per_chunk = 1;
-    hipLaunchKernelGGL(k, dim3((unsigned)((nslots + RES_WAVES - 1) / RES_WAVES), 1, 1), dim3(64 * RES_WAVES, 1, 1), pv_wave_lds_bytes(), st, q);
-    return hipGetLastError();
+    const dim3 grid((unsigned)((nslots + RES_WAVES - 1) / RES_WAVES), 1, 1), block(64 * RES_WAVES, 1, 1);
+    const PvKernelParams q = pv_resident_params(p, nslots);
+    return (!FP64 && !p.fwd64) ? pv_launch_instance<pv_wave_kernel_1024<S_ROWS, false, true, false, !FP64>>(grid, block, pv_wave_lds_bytes(), st, q)
+                               : pv_launch_instance<pv_wave_kernel_1024<S_ROWS, false, true, false, false>>(grid, block, pv_wave_lds_bytes(), st, q);
 }
 
 }  // namespace

@@ -26,9 +26,7 @@
 #include "pv_kernels.h"
 #include "pv_device_common.h"
 #include "pv_pk_math.h"
-#ifndef PV_WG16_WPS
-#define PV_WG16_WPS 2      // waves per SIMD the product instances are compiled for (measurement builds: 3)
-#endif
+#include "pv_residue.h"
 #ifndef PV_WG16_WPS
 #define PV_WG16_WPS 2      // waves per SIMD the product instances are compiled for (measurement builds: 3 -> 168 VGPRs, 99 spilled at N = 8192 / hop N/4: tools/experiments/README.md)
 #endif
@@ -405,73 +403,8 @@ __device__ __forceinline__ void fft_wg16_inv_d(double2 (&a)[16], double2 *S, con
     radix16_inv_d(a);
 }
 
-// v * exp(+2 pi j ridx / N) in doubles (rotate_route's fp64 twin)
-template <int R_, int LOG2N_>
-__device__ __forceinline__ double2 rotate_route_d(unsigned route, double2 v, const double2 *__restrict__ tw64)
-{
-    const unsigned ridx = (route >> 16) & ((1u << LOG2N_) - 1u);
-    if (R_ == 4) { const unsigned q = ridx >> (LOG2N_ - 2); return q == 0 ? v : q == 1 ? double2{-v.y, v.x} : q == 2 ? double2{-v.x, -v.y} : double2{v.y, -v.x}; }   // j^q exactly
-    const double2 w = tw64[ridx];
-    return double2{__fma_rn(v.x, w.x, __dmul_rn(v.y, w.y)), __fma_rn(v.y, w.x, -__dmul_rn(v.x, w.y))};
-}
 template <int R_, int LOG2N_> __device__ __forceinline__ float2 rotate_any(unsigned route, float2 v, const float2 *tw32, const double2 *) { return rotate_route<R_, LOG2N_>(route, v, tw32); }
 template <int R_, int LOG2N_> __device__ __forceinline__ double2 rotate_any(unsigned route, double2 v, const float2 *, const double2 *tw64) { return rotate_route_d<R_, LOG2N_>(route, v, tw64); }
-
-// o * W_32^r (fp64, split pass) and o * exp(+2 pi j r / 32) (packed fp32, c2r pass), r = 0..7 compile-time: the row part of W_8192^{t + 256 r}
-__device__ __forceinline__ double2 mul_w32_16(double2 o, int r)
-{
-    constexpr double c[9] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440,
-                             0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785, 0.0};
-    if (r == 0) return o;
-    return cmul(o, double2{c[r], -c[8 - r]});
-}
-__device__ __forceinline__ pk::c32 mul_w32_inv_pk16(pk::c32 o, int r)
-{
-    constexpr float c[9] = {1.0f, 0.98078528040323044913f, 0.92387953251128675613f, 0.83146961230254523708f, 0.70710678118654752440f,
-                            0.55557023301960222474f, 0.38268343236508977173f, 0.19509032201612826785f, 0.0f};
-    if (r == 0) return o;
-    return pk::cmul(o, pk::c32{c[r], c[8 - r]});
-}
-
-// Workgroup-wide claim rounds (pv_wg_kernel.hip): atomic MIN on the claim word, the smallest pending source bin wins the round.  CLAIM[0..H) all-ones on entry and exit.
-template <int NS, int H_, typename V2>
-__device__ __forceinline__ void claim_rounds_wg16(const unsigned (&rt)[NS], const V2 (&ys)[NS], const int (&id)[NS], V2 *Y, unsigned *CLAIM)
-{
-    unsigned pend = 0;
-    unsigned tg[NS];
-#pragma unroll
-    for (int r = 0; r < NS; r++) {
-        const unsigned t = rt[r] & 0xFFFFu;
-        const bool ok = t < (unsigned)H_;
-        pend |= ok ? (1u << r) : 0u;
-        tg[r] = ok ? t : 0u;
-    }
-    while (__syncthreads_or(pend != 0u)) {
-#pragma unroll
-        for (int r = 0; r < NS; r++) if (pend & (1u << r)) atomicMin(&CLAIM[tg[r]], (unsigned)id[r]);
-        __syncthreads();
-        unsigned c[NS];
-        V2 o[NS];
-#pragma unroll
-        for (int r = 0; r < NS; r++) c[r] = CLAIM[tg[r]];
-#pragma unroll
-        for (int r = 0; r < NS; r++) o[r] = Y[tg[r]];
-#pragma unroll
-        for (int r = 0; r < NS; r++) {
-            if ((pend & (1u << r)) && c[r] == (unsigned)id[r]) {
-                Y[tg[r]] = V2{o[r].x + ys[r].x, o[r].y + ys[r].y};
-                CLAIM[tg[r]] = 0xFFFFFFFFu;
-                pend &= ~(1u << r);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ int digitrev4_16(int v, int nd)
-{
-    const unsigned r = __brev((unsigned)v) >> (32 - 2 * nd);
-    return (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
-}
 
 // Rare path: above-Nyquist residue of fft.js's in-place real DIT, one quarter of the buffer at a time (log2 N odd: radix-2 base blocks, bundle:447-463,
 // then the radix-4 stages with their predicated stores, bundle:329-441), then its sources are added into Y.  See residue_scatter_wg.
@@ -508,10 +441,10 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg16(co
                 const int lb = t + T * i;
                 float a, b, c, d;
                 if (base == N / 2) {                                       // quarter 2: sub-FFT of xw[4n + 2], from the frame's stash
-                    const int off = digitrev4_16(N / 8 + lb, nd);          // = 2 (mod 4): sample off + q N/4 is XQ[(off - 2) / 4 + q N/16]
+                    const int off = digitrev4(N / 8 + lb, nd);          // = 2 (mod 4): sample off + q N/4 is XQ[(off - 2) / 4 + q N/16]
                     a = XQ[(off - 2) >> 2]; b = XQ[((off - 2) >> 2) + N / 16]; c = XQ[((off - 2) >> 2) + N / 8]; d = XQ[((off - 2) >> 2) + 3 * N / 16];
                 } else {
-                    const int off = digitrev4_16(base / 4 + lb, nd);
+                    const int off = digitrev4(base / 4 + lb, nd);
                     a = mul_rounded(src.at(s0 + off), hann[off]); b = mul_rounded(src.at(s0 + off + N / 4), hann[off + N / 4]);
                     c = mul_rounded(src.at(s0 + off + N / 2), hann[off + N / 2]); d = mul_rounded(src.at(s0 + off + 3 * N / 4), hann[off + 3 * N / 4]);
                 }
@@ -526,7 +459,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg16(co
 #pragma unroll
             for (int i = 0; i < 4; i++) {                                  // QN / 2 = 4T radix-2 blocks per quarter (bundle:447-463)
                 const int lb = t + T * i;
-                const int off = digitrev4_16((base == N / 2 ? N / 4 : base / 2) + lb, nd);
+                const int off = digitrev4((base == N / 2 ? N / 4 : base / 2) + lb, nd);
                 float a, b;
                 if (base == N / 2) { a = XQ[(off - 2) >> 2]; b = XQ[((off - 2) >> 2) + N / 8]; }     // quarter 2: sub-FFT of xw[4n + 2], from the frame's stash
                 else { a = mul_rounded(src.at(s0 + off), hann[off]); b = mul_rounded(src.at(s0 + off + N / 2), hann[off + N / 2]); }
@@ -584,7 +517,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg16(co
 #pragma unroll
             for (int j = 0; j < 8; j++) if (rt[j] != NOROUTE) Y[rt[j] & 0xFFFFu] = ys[j];
         } else {
-            claim_rounds_wg16<8, H>(rt, ys, id, Y, CLAIM);
+            claim_rounds_wg<8, H>(rt, ys, id, Y, CLAIM);
         }
         __syncthreads();
         RES_MARK(7);
@@ -593,85 +526,30 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg16(co
 
 // fp64 flavour: the same stage structure in doubles -- every quarter from the source samples (the window product rounded to fp32 as the reference's Float32Array does,
 // pv:55), the three stage twiddles table entries like fft.js's (bundle:329-441), the sources added by claim rounds.
+template <int LOG2N_, int R_>
+struct ResidueWg16D {
+    using C = QC<LOG2N_>;
+    using V2 = double2;
+    static constexpr int LOG2N = LOG2N_, T = C::T, ID0 = C::N / 2;
+    static constexpr bool UNROLL_STAGES = false;
+    WaveSrc src; long s0; const float *hann; const double2 *tw64;
+    double2 *Y; unsigned *CLAIM; double2 *Qp;
+    __device__ __forceinline__ double2 *Q() const { return Qp; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    __device__ __forceinline__ double sample(int, int smp) const { return (double)mul_rounded(src.at(s0 + smp), hann[smp]); }
+    __device__ __forceinline__ void twiddles(int i, int, int tws, double2 &w1, double2 &w2, double2 &w3) const { w1 = tw64[i << tws]; w2 = tw64[2 * (i << tws)]; w3 = tw64[3 * (i << tws)]; }
+    __device__ __forceinline__ double2 rotate(unsigned route, double2 v) const { return rotate_route_d<R_, LOG2N_>(route, v, tw64); }
+    __device__ __forceinline__ void add(const unsigned (&rt)[8], const double2 (&ys)[8], const int (&id)[8]) const { claim_rounds_wg<8, C::H>(rt, ys, id, Y, CLAIM); __syncthreads(); }
+};
 template <int LOG2N, int R_>
 __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg16_d(const float *in, const float *hist, int hist_len, bool sys, long s0, const float *__restrict__ hann,
                                                                                  const double2 *__restrict__ tw64, int t, int upper_end, int up_delta, unsigned up_ridx, double *dbg_X)
 {
     using C = QC<LOG2N>;
-    constexpr int N = C::N, H = C::H, T = C::T, QN = N / 4;
-    constexpr bool BASE4 = (LOG2N % 2) == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double2 *Y = reinterpret_cast<double2 *>(smem + C::OFF_Y);
-    unsigned *CLAIM = reinterpret_cast<unsigned *>(smem + C::OFF_ROUTE);
-    double2 *Q = reinterpret_cast<double2 *>(smem + C::OFF_RESQ);
-    const WaveSrc src{in, hist, hist_len, sys};
-    auto xw = [&](int off) -> double { return (double)mul_rounded(src.at(s0 + off), hann[off]); };
-    for (int base = N / 2; base < N && base < upper_end; base += QN) {
-        if (BASE4) {
-            constexpr int nd = (LOG2N - 2) / 2;
-#pragma unroll
-            for (int i = 0; i < 2; i++) {
-                const int lb = t + T * i;
-                const int off = digitrev4_16(base / 4 + lb, nd);
-                const double a = xw(off), b = xw(off + N / 4), c = xw(off + N / 2), d = xw(off + 3 * N / 4);
-                const double t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
-                Q[4 * lb] = double2{t0 + t2, 0.0};
-                Q[4 * lb + 1] = double2{t1, -t3};
-                Q[4 * lb + 2] = double2{t0 - t2, 0.0};
-                Q[4 * lb + 3] = double2{t1, t3};
-            }
-        } else {
-            constexpr int nd = (LOG2N - 1) / 2;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int lb = t + T * i;
-                const int off = digitrev4_16(base / 2 + lb, nd);
-                const double a = xw(off), b = xw(off + N / 2);
-                Q[2 * lb] = double2{a + b, 0.0};
-                Q[2 * lb + 1] = double2{a - b, 0.0};
-            }
-        }
-        __syncthreads();
-        constexpr int LOG2BASE = BASE4 ? 2 : 1;
-        for (int log2m = LOG2BASE + 2; log2m <= LOG2N - 2; log2m += 2) {
-            const int q = (1 << log2m) >> 2, hq = q >> 1;
-            const int nblocks = QN >> log2m;
-            const int tws = LOG2N - log2m;
-            for (int u = t; u < nblocks * (hq + 1); u += T) {
-                int blk, i;
-                if (u < nblocks * hq) { blk = u / hq; i = u - blk * hq; } else { blk = u - nblocks * hq; i = hq; }
-                const int o = blk << log2m;
-                const double2 A = Q[o + i];
-                const double2 Bv = cmul(Q[o + q + i], tw64[i << tws]);
-                const double2 Cc = cmul(Q[o + 2 * q + i], tw64[2 * (i << tws)]);
-                const double2 D = cmul(Q[o + 3 * q + i], tw64[3 * (i << tws)]);
-                const double2 T0 = cadd(A, Cc), T1 = csub(A, Cc), T2 = cadd(Bv, D), T3 = csub(Bv, D);
-                Q[o + i] = cadd(T0, T2);
-                Q[o + q + i] = double2{T1.x + T3.y, T1.y - T3.x};
-                if (i == 0) {
-                    Q[o + 2 * q] = csub(T0, T2);
-                } else if (i != hq) {
-                    Q[o + q - i] = double2{T1.x - T3.y, -(T1.y + T3.x)};
-                    Q[o + 2 * q - i] = double2{T0.x - T2.x, -(T0.y - T2.y)};
-                }
-            }
-            __syncthreads();
-        }
-        if (dbg_X)
-            for (int i = t; i < QN; i += T) if (base + i >= H) { dbg_X[2 * (base + i)] = Q[i].x; dbg_X[2 * (base + i) + 1] = Q[i].y; }
-        unsigned rt[8];
-        double2 ys[8];
-        int id[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int b = base + t + T * j, tgt = b + up_delta;
-            rt[j] = (b >= H && b < upper_end && tgt >= 0 && tgt < H) ? ((up_ridx << 16) | (unsigned)tgt) : NOROUTE;
-            ys[j] = rotate_route_d<R_, LOG2N>(rt[j], Q[t + T * j], tw64);
-            id[j] = b - N / 2;
-        }
-        claim_rounds_wg16<8, H>(rt, ys, id, Y, CLAIM);
-        __syncthreads();
-    }
+    const ResidueWg16D<LOG2N, R_> k{WaveSrc{in, hist, hist_len, sys}, s0, hann, tw64, reinterpret_cast<double2 *>(smem + C::OFF_Y),
+                                    reinterpret_cast<unsigned *>(smem + C::OFF_ROUTE), reinterpret_cast<double2 *>(smem + C::OFF_RESQ)};
+    residue_quarters(k, t, upper_end, up_delta, up_ridx, dbg_X);
 }
 
 // S_ROWS = hop / (N / 16) in {2, 4, 8, 16}: the frame advances by whole register rows (N / 16 samples), overlap-add accumulator and input window live in registers.
@@ -719,22 +597,8 @@ __global__ __launch_bounds__(QC<LOG2N>::T, (RESIDENT || FP64W) ? 1 : PV_WG16_WPS
 resident_top:
     if (RESIDENT) {
         unsigned *BC = reinterpret_cast<unsigned *>(smem + C::OFF_OCC + 48);
-        if (t == 0) {
-            unsigned word;
-            const unsigned long long idle0 = wall_clock64();
-            for (;;) {
-                word = __hip_atomic_load(p.ctl + 16 + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if ((word & 0xFFFFu) != (last_seq & 0xFFFFu)) break;
-                if (__hip_atomic_load(p.ctl + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || wall_clock64() - idle0 > (unsigned long long)p.idle_ticks) { word = 0u; break; }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            BC[0] = word;
-        }
-        __syncthreads();
-        const unsigned word = BC[0];
-        __syncthreads();
+        const unsigned word = resident_poll_wg(p.ctl, ch, last_seq, p.idle_ticks, BC, t);
         if (word == 0u) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
         const unsigned seq = word & 0xFFFFu, nch_now = (word >> 16) & 0x7Fu, cur = (word >> 23) & 1u;
         t0_mod_n = (int)(((word >> 24) & 0xFFu) * HOP) & (N - 1);
         hist_in = p.hist2[cur]; hist_out = p.hist2[cur ^ 1u];
@@ -848,7 +712,7 @@ resident_top:
                 const double2 zm = (k == 0) ? z[0] : S64[8 * T - k];          // element M - k sits at (M - k) - 8T of the stored rows
                 const double2 E{z[r].x + zm.x, z[r].y - zm.y};
                 const double2 O{z[r].x - zm.x, z[r].y + zm.y};
-                const double2 WO = cmul(wl, mul_w32_16(O, r));
+                const double2 WO = cmul(wl, mul_w32(O, r));
                 double2 xa{E.x + WO.y, E.y - WO.x};
                 double2 xb{E.x - WO.y, -(E.y + WO.x)};
                 if (r == 0 && tq == 0) {
@@ -1101,8 +965,8 @@ resident_top:
 #pragma unroll
                 for (int r = 0; r < 16; r++) CLAIM[tq + T * r] = 0xFFFFFFFFu;
                 if (tq == 0) CLAIM[M] = 0xFFFFFFFFu;
-                claim_rounds_wg16<9, H>(rt0, ys0, id0, Yd, CLAIM);
-                claim_rounds_wg16<9, H>(rt1, ys1, id1, Yd, CLAIM);
+                claim_rounds_wg<9, H>(rt0, ys0, id0, Yd, CLAIM);
+                claim_rounds_wg<9, H>(rt1, ys1, id1, Yd, CLAIM);
                 if (need_res) {
                     __syncthreads();
                     const int up_delta = last_shift;
@@ -1189,8 +1053,8 @@ resident_top:
 #pragma unroll
                     for (int r = 0; r < 16; r++) CLAIM[tq + T * r] = 0xFFFFFFFFu;
                     if (tq == 0) CLAIM[M] = 0xFFFFFFFFu;
-                    claim_rounds_wg16<9, H>(rt0, ys0, id0, Y, CLAIM);            // (its first barrier orders the fill before the first claims)
-                    claim_rounds_wg16<9, H>(rt1, ys1, id1, Y, CLAIM);
+                    claim_rounds_wg<9, H>(rt0, ys0, id0, Y, CLAIM);            // (its first barrier orders the fill before the first claims)
+                    claim_rounds_wg<9, H>(rt1, ys1, id1, Y, CLAIM);
                     if (need_res) {
                         __syncthreads();
                         const int up_delta = last_shift;
@@ -1207,7 +1071,7 @@ resident_top:
                                 id2[j] = b - N / 2;
                                 if (dbg && b < upper_end) { p.dbg_X[2 * b] = s2v[j].x; p.dbg_X[2 * b + 1] = s2v[j].y; }
                             }
-                            claim_rounds_wg16<4, H>(rt2, ys2, id2, Y, CLAIM);
+                            claim_rounds_wg<4, H>(rt2, ys2, id2, Y, CLAIM);
                         }
                     }
                 }
@@ -1255,7 +1119,7 @@ resident_top:
                 double2 yk = Yd[k], ym = Yd[M - k];
                 if (k == 0) { yk.y = 0.0; ym.y = 0.0; }
                 const double2 E{yk.x + ym.x, yk.y - ym.y}, O{yk.x - ym.x, yk.y + ym.y};
-                const double2 c = cmul(cconj(mul_w32_16(cconj(O), r)), wlc);   // O * exp(+2 pi j r / 32) * exp(+2 pi j tq / N)
+                const double2 c = cmul(cconj(mul_w32(cconj(O), r)), wlc);   // O * exp(+2 pi j r / 32) * exp(+2 pi j tq / N)
                 zd[r] = double2{(E.x - c.y) * sc, (E.y + c.x) * sc};        // E + j c
                 zb[r] = double2{(E.x + c.y) * sc, -(E.y - c.x) * sc};       // conj(E - j c)
             }
@@ -1279,7 +1143,7 @@ resident_top:
                 pk::c32 yk = Yc[k], ym = Yc[M - k];
                 if (k == 0) { yk.y = 0.f; ym.y = 0.f; }
                 const pk::c32 E = pk::add_conj(yk, ym), O = pk::sub_conj(yk, ym);
-                const pk::c32 c = pk::cmul(mul_w32_inv_pk16(O, r), wlfs);
+                const pk::c32 c = pk::cmul(mul_w32_inv_pk(O, r), wlfs);
                 zi[r] = pk::fma_addj(E, scsc, c);
                 zb[r] = pk::fma_conj_subj(E, scsc, c);
             }
@@ -1366,30 +1230,14 @@ template <int LOG2N, int S_ROWS, bool AUX>
 hipError_t launch_wg16(const PvKernelParams &p, int nch, int nchunks, hipStream_t st)
 {
     using C = QC<LOG2N>;
-    static std::atomic<bool> attr_done[16];
-    auto k = pv_wg16_kernel<LOG2N, S_ROWS, AUX>;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(k), C::LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(nchunks, nch, 1), dim3(C::T, 1, 1), C::LDS_BYTES, st, p);
-    return hipGetLastError();
+    return pv_launch_instance<pv_wg16_kernel<LOG2N, S_ROWS, AUX>>(dim3(nchunks, nch, 1), dim3(C::T, 1, 1), C::LDS_BYTES, st, p);
 }
 
 template <int LOG2N, int S_ROWS>
 hipError_t launch_wg16_resident(const PvKernelParams &p, int nslots, hipStream_t st)
 {
     using C = QC<LOG2N>;
-    static std::atomic<bool> attr_done[16];
-    auto k = pv_wg16_kernel<LOG2N, S_ROWS, false, true>;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(k), C::LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    PvKernelParams q = p;
-    q.nchunks = 1; q.nch = nslots; q.nhops = 1; q.frames_per_chunk = 1;
-    hipLaunchKernelGGL(k, dim3(1, nslots, 1), dim3(C::T, 1, 1), C::LDS_BYTES, st, q);
-    return hipGetLastError();
+    return pv_launch_instance<pv_wg16_kernel<LOG2N, S_ROWS, false, true>>(dim3(1, nslots, 1), dim3(C::T, 1, 1), C::LDS_BYTES, st, pv_resident_params(p, nslots));
 }
 
 template <int LOG2N>

@@ -252,61 +252,6 @@ __device__ __forceinline__ void fft_wg_inv_pk(pk::c32 (&a)[8], pk::c32 *S, const
     }
 }
 
-// o * exp(+2 pi j r / 16), r = 0..3 (compile-time): the wave-uniform part of the c2r twiddle, packed
-__device__ __forceinline__ pk::c32 mul_w16_inv_pk_wg(pk::c32 o, int r)
-{
-    const float c = 0.92387953251128675613f, sn = 0.38268343236508977173f, h = 0.70710678118654752440f;
-    switch (r) {
-    case 0: return o;
-    case 1: return pk::cmul(o, pk::c32{c, sn});
-    case 2: return pk::mul(pk::add_j(o, o), pk::c32{h, h});
-    default: return pk::cmul(o, pk::c32{sn, c});
-    }
-}
-
-// Workgroup-wide claim rounds (see claim_rounds in pv_wave_kernel.hip): the loop condition is reduced over the workgroup, and -- because
-// several waves race for a claim word here -- a source posts its bin with an LDS atomic MIN: the smallest pending source bin wins the round,
-// so every target accumulates its contributions in ascending source order (the order of the reference's loops, pv:122,146) whatever the
-// timing of the waves; results are reproducible bit for bit for every f.  CLAIM[0..H) must be all-ones on entry and is all-ones on exit.
-template <int NS, int H_>
-__device__ __forceinline__ void claim_rounds_wg(const unsigned (&rt)[NS], const float2 (&ys)[NS], const int (&id)[NS], float2 *Y, unsigned *CLAIM)
-{
-    unsigned pend = 0;
-    unsigned tg[NS];
-#pragma unroll
-    for (int r = 0; r < NS; r++) {
-        const unsigned t = rt[r] & 0xFFFFu;
-        const bool ok = t < (unsigned)H_;                                  // valid route <=> target field < H
-        pend |= ok ? (1u << r) : 0u;
-        tg[r] = ok ? t : 0u;
-    }
-    while (__syncthreads_or(pend != 0u)) {
-#pragma unroll
-        for (int r = 0; r < NS; r++) if (pend & (1u << r)) atomicMin(&CLAIM[tg[r]], (unsigned)id[r]);
-        __syncthreads();
-        unsigned c[NS];
-        float2 o[NS];
-#pragma unroll
-        for (int r = 0; r < NS; r++) c[r] = CLAIM[tg[r]];                   // independent reads first, then the winners' stores (see pv_wave_kernel.hip)
-#pragma unroll
-        for (int r = 0; r < NS; r++) o[r] = Y[tg[r]];
-#pragma unroll
-        for (int r = 0; r < NS; r++) {
-            if ((pend & (1u << r)) && c[r] == (unsigned)id[r]) {
-                Y[tg[r]] = float2{o[r].x + ys[r].x, o[r].y + ys[r].y};
-                CLAIM[tg[r]] = 0xFFFFFFFFu;                                // only the winner touches the word; losers re-post after the barrier
-                pend &= ~(1u << r);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ int digitrev4_(int v, int nd)
-{
-    if (nd == 0) return 0;
-    const unsigned r = __brev((unsigned)v) >> (32 - 2 * nd);
-    return (int)(((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u));
-}
 
 // Rare path: above-Nyquist residue of fft.js's in-place real DIT, one quarter of the buffer at a time, then its sources
 // are added into Y.  Same structure as residue_scatter_1024, any LOG2N (radix-2 base stage when log2 N is odd: bundle:447-463).
@@ -331,7 +276,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg(cons
     for (int base = N / 2; base < N && base < upper_end; base += QN) {
         if (base == N / 2) {
             if (BASE4) {
-                const int off = digitrev4_(N / 8 + t, (LOG2N - 2) / 2);      // = 2 (mod 4): sample off + q N/4 is XQ[(off - 2) / 4 + q N/16]
+                const int off = digitrev4(N / 8 + t, (LOG2N - 2) / 2);      // = 2 (mod 4): sample off + q N/4 is XQ[(off - 2) / 4 + q N/16]
                 const float a = XQ[(off - 2) >> 2], b = XQ[((off - 2) >> 2) + N / 16], c = XQ[((off - 2) >> 2) + N / 8], d = XQ[((off - 2) >> 2) + 3 * N / 16];
                 const float t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
                 Q[4 * t] = float2{t0 + t2, 0.f};
@@ -341,7 +286,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg(cons
             } else {
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
-                    const int lb = t + T * i, off = digitrev4_(N / 4 + lb, (LOG2N - 1) / 2);
+                    const int lb = t + T * i, off = digitrev4(N / 4 + lb, (LOG2N - 1) / 2);
                     const float a = XQ[(off - 2) >> 2], b = XQ[((off - 2) >> 2) + N / 8];
                     Q[2 * lb] = float2{a + b, 0.f};
                     Q[2 * lb + 1] = float2{a - b, 0.f};
@@ -350,7 +295,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg(cons
         } else if (BASE4) {
             constexpr int nd = (LOG2N - 2) / 2;
             const int blk = base / 4 + t;                                  // QN/4 = T blocks per quarter
-            const int off = digitrev4_(blk, nd);
+            const int off = digitrev4(blk, nd);
             const float a = mul_rounded(src.at(s0 + off), hann[off]), b = mul_rounded(src.at(s0 + off + N / 4), hann[off + N / 4]);
             const float c = mul_rounded(src.at(s0 + off + N / 2), hann[off + N / 2]), d = mul_rounded(src.at(s0 + off + 3 * N / 4), hann[off + 3 * N / 4]);
             const float t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
@@ -363,7 +308,7 @@ __device__ __attribute__((noinline)) PV_NO_DS_MERGE void residue_scatter_wg(cons
 #pragma unroll
             for (int i = 0; i < 2; i++) {                                  // QN/2 = 2T blocks per quarter
                 const int lb = t + T * i, blk = base / 2 + lb;
-                const int off = digitrev4_(blk, nd);
+                const int off = digitrev4(blk, nd);
                 const float a = mul_rounded(src.at(s0 + off), hann[off]), b = mul_rounded(src.at(s0 + off + N / 2), hann[off + N / 2]);
                 Q[2 * lb] = float2{a + b, 0.f};
                 Q[2 * lb + 1] = float2{a - b, 0.f};
@@ -487,22 +432,8 @@ __global__ __launch_bounds__(64 << (LOG2N - 10), 2) PV_NO_DS_MERGE void pv_wg_ke
 resident_top:
     if (RESIDENT) {
         unsigned *BC = reinterpret_cast<unsigned *>(smem + C::OFF_OCC);  // broadcast slot (the peak search's wave masks: not live here)
-        if (t == 0) {
-            unsigned word;
-            const unsigned long long idle0 = wall_clock64();
-            for (;;) {
-                word = __hip_atomic_load(p.ctl + 16 + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if ((word & 0xFFFFu) != (last_seq & 0xFFFFu)) break;
-                if (__hip_atomic_load(p.ctl + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || wall_clock64() - idle0 > (unsigned long long)p.idle_ticks) { word = 0u; break; }   // asked to leave / ~50 ms idle
-                __builtin_amdgcn_s_sleep(2);
-            }
-            BC[0] = word;
-        }
-        __syncthreads();
-        const unsigned word = BC[0];
-        __syncthreads();
-        if (word == 0u) return;                                          // (a sequence number is never 0)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        const unsigned word = resident_poll_wg(p.ctl, ch, last_seq, p.idle_ticks, BC, t);
+        if (word == 0u) return;                                          // asked to leave / ~50 ms idle (a sequence number is never 0)
         const unsigned seq = word & 0xFFFFu, nch_now = (word >> 16) & 0x7Fu, cur = (word >> 23) & 1u;
         t0_mod_n = (int)(((word >> 24) & 0xFFu) * HOP) & (N - 1);
         hist_in = p.hist2[cur]; hist_out = p.hist2[cur ^ 1u];
@@ -954,7 +885,7 @@ resident_top:
                 pk::c32 yk = Yc[k], ym = Yc[M - k];
                 if (k == 0) { yk.y = 0.f; ym.y = 0.f; }
                 const pk::c32 E = pk::add_conj(yk, ym), O = pk::sub_conj(yk, ym);
-                const pk::c32 c = pk::cmul(mul_w16_inv_pk_wg(O, r), wlfs);
+                const pk::c32 c = pk::cmul(mul_w16_inv_pk(O, r), wlfs);
                 zi[r] = pk::fma_addj(E, scsc, c);
                 zb[r] = pk::fma_conj_subj(E, scsc, c);
             }
@@ -1056,33 +987,15 @@ template <int LOG2N, int S_ROWS, bool AUX>
 hipError_t launch_wg(const PvKernelParams &p, int nch, int nchunks, hipStream_t st)
 {
     constexpr int G = 1 << (LOG2N - 10);
-    static std::atomic<bool> attr_done[16];
-    auto k = pv_wg_kernel<LOG2N, S_ROWS, AUX>;
-    using CR = WgCfg<G, true>;
-    constexpr int lds_bytes = S_ROWS ? WgCfg<G>::LDS_BYTES : CR::LDS_BYTES_RING;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(k), lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(nchunks, nch, 1), dim3(64 * G, 1, 1), lds_bytes, st, p);
-    return hipGetLastError();
+    constexpr int lds_bytes = S_ROWS ? WgCfg<G>::LDS_BYTES : WgCfg<G, true>::LDS_BYTES_RING;
+    return pv_launch_instance<pv_wg_kernel<LOG2N, S_ROWS, AUX>>(dim3(nchunks, nch, 1), dim3(64 * G, 1, 1), lds_bytes, st, p);
 }
 
 template <int LOG2N, int S_ROWS>
 hipError_t launch_wg_resident(const PvKernelParams &p, int nslots, hipStream_t st)
 {
     constexpr int G = 1 << (LOG2N - 10);
-    static std::atomic<bool> attr_done[16];
-    auto k = pv_wg_kernel<LOG2N, S_ROWS, false, true>;
-    constexpr int lds_bytes = WgCfg<G>::LDS_BYTES;
-    {
-        const hipError_t e = pv_set_dynamic_lds_once(attr_done, reinterpret_cast<const void *>(k), lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    PvKernelParams q = p;
-    q.nchunks = 1; q.nch = nslots; q.nhops = 1; q.frames_per_chunk = 1;
-    hipLaunchKernelGGL(k, dim3(1, nslots, 1), dim3(64 * G, 1, 1), lds_bytes, st, q);
-    return hipGetLastError();
+    return pv_launch_instance<pv_wg_kernel<LOG2N, S_ROWS, false, true>>(dim3(1, nslots, 1), dim3(64 * G, 1, 1), WgCfg<G>::LDS_BYTES, st, pv_resident_params(p, nslots));
 }
 
 template <int LOG2N>

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """A/B timing of library builds on the BASELINE shapes, one process per build (PHAZE_LIB is read at import): prints one line per shape with the
 HIP-event time of a resident launch and the parity of its first hops against the oracle.  Design aid (tools/ab.sh), not part of the product.
-    PHAZE_LIB=build/exp/libphaze_x.so python tools/ab_shapes.py label shape[,shape...] [steps]
+    PHAZE_LIB=build/exp/libphaze_x.so python tools/ab_shapes.py label shape[,shape...] [steps] [flags]
+flags: pv_config.flags of the handles (4 = PV_FLAG_WORKGROUP_KERNEL: the eight-element workgroup kernel at N = 2048 / 4096 / 8192); default 0
 shapes: head headf08 headf07 headf06 headsweep c3 c3f15 c3f07 c4 c4f08 c5 c5f08 c5f07 c5f06 c5sweep native nativef08 h128 h512"""
 import os
 import sys
@@ -28,6 +29,7 @@ SH = {  # fft, hop, nch, T, cps, pitch
 def main():
     label, shapes = sys.argv[1], sys.argv[2].split(",")
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+    flags = int(sys.argv[4]) if len(sys.argv) > 4 else 0
     sys.path.insert(0, ROOT)
     import bench
     dev = torch.device("cuda", 0)
@@ -37,7 +39,7 @@ def main():
         y = torch.empty_like(x)
         pt = (0.5 + 1.5 * (torch.arange(T, device=dev) % 64).float() / 63.0) if pf == "sweep" else torch.full((T,), float(pf), device=dev)
         pt = pt.float().contiguous()
-        pv = phaze_amd.PhaseVocoder(fft_size=fft, hop_size=hop, max_channels=nch, max_hops=1)
+        pv = phaze_amd.PhaseVocoder(fft_size=fft, hop_size=hop, max_channels=nch, max_hops=1, flags=flags)
         st = torch.cuda.Stream(device=dev)
         pv.set_stream(st.cuda_stream)
         run = lambda: pv.process_batch_device(x.data_ptr(), y.data_ptr(), nch, T, T * hop, pt.data_ptr(), 0, cps)

@@ -254,22 +254,63 @@ def pinned_empty(shape, dtype=np.float32):
     return np.frombuffer(buf, dtype=dt, count=n).reshape(shape)
 
 
-class PhaseVocoder:
+class _Handle:
+    """What the four handle classes share: create-and-raise, close, the status check and reset / set_stream / synchronize.  `_prefix` is the C
+    prefix of the handle type's entry points (<prefix>_create, _destroy, _last_error, _reset, _set_stream, _synchronize)."""
+
+    _prefix = None
+    _fft_size_is_value_error = True     # PV_ERR_FFT_SIZE from create raises ValueError: the reference throws Error('FFT size must be ...') (bundle:6-7)
+    _owned = True                       # close() destroys the handle (False: borrowed from the handle that owns it)
+
+    def _bind(self, handle=None):
+        self._L = load_library()
+        self._h = C.c_void_p(handle)
+        self._destroy, self._last_error, self._reset, self._set_stream, self._synchronize = (
+            getattr(self._L, f"{self._prefix}_{n}") for n in ("destroy", "last_error", "reset", "set_stream", "synchronize"))
+
+    def _create(self, cfg):
+        self._bind()
+        rc = getattr(self._L, self._prefix + "_create")(C.byref(cfg), C.byref(self._h))
+        if rc != PV_OK:
+            msg = self._last_error(None).decode()
+            self._h = C.c_void_p()
+            if rc == PV_ERR_FFT_SIZE and self._fft_size_is_value_error:
+                raise ValueError(msg)
+            raise PvError(rc, msg)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and self._owned:
+            self._destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != PV_OK:
+            raise PvError(rc, self._last_error(self._h).decode())
+
+    def reset(self):
+        self._check(self._reset(self._h))
+
+    def set_stream(self, hip_stream):
+        self._check(self._set_stream(self._h, C.c_void_p(hip_stream)))
+
+    def synchronize(self):
+        self._check(self._synchronize(self._h))
+
+
+class PhaseVocoder(_Handle):
     """One processor instance = one `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43)."""
 
+    _prefix = "pv"
     parameter_descriptors = [{"name": "pitchFactor", "defaultValue": 1.0}]   # phase-vocoder.js:17-22
 
     def __init__(self, fft_size=2048, hop_size=128, max_channels=2, max_hops=1, device_id=0, frames_per_chunk=0, flags=0):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        cfg = make_config(fft_size, hop_size, max_channels, max_hops, device_id, frames_per_chunk, flags)
-        rc = self._L.pv_create(C.byref(cfg), C.byref(self._h))
-        if rc != PV_OK:
-            msg = self._L.pv_last_error(None).decode()
-            self._h = C.c_void_p()
-            if rc == PV_ERR_FFT_SIZE:
-                raise ValueError(msg)           # the reference throws Error('FFT size must be ...') (bundle:6-7)
-            raise PvError(rc, msg)
+        self._create(make_config(fft_size, hop_size, max_channels, max_hops, device_id, frames_per_chunk, flags))
         self.fft_size, self.hop_size = fft_size, hop_size
         self.max_channels, self.max_hops = max_channels, max_hops
         self._host_channels = bool(flags & FLAG_HOST_CHANNEL_BOOKKEEPING)
@@ -286,24 +327,9 @@ class PhaseVocoder:
         if getattr(self, "_scratch", None) is not None:
             self._scratch.close()
             self._scratch = None
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.pv_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != PV_OK:
-            raise PvError(rc, self._L.pv_last_error(self._h).decode())
+        super().close()
 
     # -- state --
-    def reset(self):
-        self._check(self._L.pv_reset(self._h))
-
     def reset_channels(self, first, count, parts=STATE_HISTORY | STATE_ACCUMULATOR):
         self._check(self._L.pv_reset_channels_part(self._h, first, count, parts))
 
@@ -451,12 +477,6 @@ class PhaseVocoder:
         self._check(self._L.pv_process_batch_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nhops, ch_stride,
                                                     C.c_void_p(d_pitch), pitch_stride, channels_per_stream))
 
-    def set_stream(self, hip_stream):
-        self._check(self._L.pv_set_stream(self._h, C.c_void_p(hip_stream)))
-
-    def synchronize(self):
-        self._check(self._L.pv_synchronize(self._h))
-
     def forward_stats(self, reset=False):
         """(frames whose forward transform an fp32-first instance computed, frames of those that re-ran it in fp64) since creation / the last reset."""
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -536,23 +556,16 @@ def transient_plan(onsets, input_len, fft_size, nominal_hop, floor_hop, synthesi
     return hops, resets
 
 
-class TimeStretch:
+class TimeStretch(_Handle):
     """Phase-locked time stretch (pv_stretch_*): tempo change at constant pitch.  Each frame consumes `analysis_hop` input samples and emits
     `synthesis_hop` output samples, so the output lasts synthesis_hop / analysis_hop times as long; it lags the input by fft_size - synthesis_hop
     samples.  State carries across calls: any split of a stream into calls gives the same bits.  channels_per_group > 1 links consecutive channel
     slots into groups with one phase track each (pv_link_channels, link_channels): the stereo image survives the stretch."""
 
+    _prefix = "pv_stretch"
+
     def __init__(self, fft_size, analysis_hop, synthesis_hop, max_channels=1, max_frames=1, device_id=0, channels_per_group=1):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        cfg = make_stretch_config(fft_size, analysis_hop, synthesis_hop, max_channels, max_frames, device_id, 0)
-        rc = self._L.pv_stretch_create(C.byref(cfg), C.byref(self._h))
-        if rc != PV_OK:
-            msg = self._L.pv_stretch_last_error(None).decode()
-            self._h = C.c_void_p()
-            if rc == PV_ERR_FFT_SIZE:
-                raise ValueError(msg)
-            raise PvError(rc, msg)
+        self._create(make_stretch_config(fft_size, analysis_hop, synthesis_hop, max_channels, max_frames, device_id, 0))
         self.fft_size, self.analysis_hop, self.synthesis_hop = fft_size, analysis_hop, synthesis_hop
         self.max_channels, self.max_frames = max_channels, max_frames
         self.channels_per_group = 1
@@ -563,24 +576,9 @@ class TimeStretch:
                 self.close()
                 raise
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.pv_stretch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != PV_OK:
-            raise PvError(rc, self._L.pv_stretch_last_error(self._h).decode())
-
     def reset(self):
         """Zero every slot's state; the channel linking stays."""
-        self._check(self._L.pv_stretch_reset(self._h))
+        super().reset()
 
     def link_channels(self, channels_per_group):
         """pv_link_channels: slots [g G, (g + 1) G) become one group with one phase track (G = 1: every slot on its own).  Resets every slot."""
@@ -733,12 +731,6 @@ class TimeStretch:
         y = self.process_hops(x[:, :int(hops.astype(np.int64).sum())], hops, resets)
         return y, hops, resets
 
-    def set_stream(self, hip_stream):
-        self._check(self._L.pv_stretch_set_stream(self._h, C.c_void_p(hip_stream)))
-
-    def synchronize(self):
-        self._check(self._L.pv_stretch_synchronize(self._h))
-
     def export_state(self, ch):
         """(hist[N - ha], acc[N - hs], phi[N/2 + 1] u32, psi[N/2 + 1] u32) of channel slot `ch`."""
         N, H = self.fft_size, self.fft_size // 2 + 1
@@ -786,51 +778,29 @@ def resample_count(up, down, total_in):
     return int(n)
 
 
-class Resampler:
+class Resampler(_Handle):
     """Band-limited rational resampler (pv_resample_*): `up` output samples per `down` input samples, Kaiser-windowed sinc.  Output j of the stream
     sits at input position j down / up; the output lags by `latency` input samples (feed that many zeros to drain).  State carries across calls: any
     split of a stream into calls gives the same bits."""
 
+    _prefix = "pv_resample"
+    _fft_size_is_value_error = False
+
     def __init__(self, up, down, max_channels=1, max_samples=1 << 16, device_id=0, _borrowed=None):
-        self._L = load_library()
-        self._h = C.c_void_p()
         self._owned = _borrowed is None
         if _borrowed is not None:
-            self._h = C.c_void_p(_borrowed)
+            self._bind(_borrowed)
         else:
-            cfg = make_resample_config(up, down, max_channels, max_samples, device_id, 0)
-            rc = self._L.pv_resample_create(C.byref(cfg), C.byref(self._h))
-            if rc != PV_OK:
-                msg = self._L.pv_resample_last_error(None).decode()
-                self._h = C.c_void_p()
-                raise PvError(rc, msg)
+            self._create(make_resample_config(up, down, max_channels, max_samples, device_id, 0))
         l, m, w = C.c_int32(), C.c_int32(), C.c_int32()
         self._L.pv_resample_design(int(up), int(down), None, 0, C.byref(l), C.byref(m), C.byref(w))
         self.up, self.down, self.half_width, self.taps_per_phase = l.value, m.value, w.value, 2 * w.value
         self.max_channels = max_channels
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value and self._owned:
-            self._L.pv_resample_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != PV_OK:
-            raise PvError(rc, self._L.pv_resample_last_error(self._h).decode())
-
     @property
     def latency(self):
         """The output's lag in input samples (the half width W)."""
         return self.half_width
-
-    def reset(self):
-        self._check(self._L.pv_resample_reset(self._h))
 
     def out_count(self, nin):
         """What the next call of nin samples writes per channel."""
@@ -857,12 +827,6 @@ class Resampler:
         self._check(self._L.pv_resample_process_device(self._h, C.c_void_p(d_in), nch, nin, in_stride, C.c_void_p(d_out), out_stride, out_capacity, C.byref(n)))
         return n.value
 
-    def set_stream(self, hip_stream):
-        self._check(self._L.pv_resample_set_stream(self._h, C.c_void_p(hip_stream)))
-
-    def synchronize(self):
-        self._check(self._L.pv_resample_synchronize(self._h))
-
     def export_state(self, ch):
         """(hist float32[T - 1], total_in, total_out) of channel slot `ch`."""
         hist = np.zeros(self.taps_per_phase - 1, np.float32)
@@ -882,8 +846,7 @@ class _BorrowedStretch(TimeStretch):
     """The stretch handle a PitchStretch owns, seen through the TimeStretch methods (link_channels, export_state / import_state, chain_layout)."""
 
     def __init__(self, handle, fft_size, analysis_hop, synthesis_hop, max_channels):
-        self._L = load_library()
-        self._h = C.c_void_p(handle)
+        self._bind(handle)
         self.fft_size, self.analysis_hop, self.synthesis_hop = fft_size, analysis_hop, synthesis_hop
         self.max_channels, self.max_frames = max_channels, 1
         self.channels_per_group = 1
@@ -892,22 +855,15 @@ class _BorrowedStretch(TimeStretch):
         self._h = C.c_void_p()                          # owned by the pitch handle
 
 
-class PitchStretch:
+class PitchStretch(_Handle):
     """Pitch shifting through the time stretch (pv_pitch_*): a TimeStretch followed by a Resampler at up / down on one stream, the stretched signal
     staying on the device.  Pitch factor down / up, duration factor (synthesis_hop / analysis_hop) (up / down); up = down = 0 means analysis_hop /
     synthesis_hop: constant duration, pitch x synthesis_hop / analysis_hop.  `.stretch` and `.resampler` are the inner handles."""
 
+    _prefix = "pv_pitch"
+
     def __init__(self, fft_size, analysis_hop, synthesis_hop, up=0, down=0, max_channels=1, max_frames=1, channels_per_group=1, device_id=0):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        cfg = make_pitch_config(fft_size, analysis_hop, synthesis_hop, up, down, max_channels, max_frames, device_id, 0)
-        rc = self._L.pv_pitch_create(C.byref(cfg), C.byref(self._h))
-        if rc != PV_OK:
-            msg = self._L.pv_pitch_last_error(None).decode()
-            self._h = C.c_void_p()
-            if rc == PV_ERR_FFT_SIZE:
-                raise ValueError(msg)
-            raise PvError(rc, msg)
+        self._create(make_pitch_config(fft_size, analysis_hop, synthesis_hop, up, down, max_channels, max_frames, device_id, 0))
         self.fft_size, self.analysis_hop, self.synthesis_hop = fft_size, analysis_hop, synthesis_hop
         self.max_channels = max_channels
         if up == 0 and down == 0:
@@ -925,32 +881,12 @@ class PitchStretch:
         if getattr(self, "_h", None) and self._h.value:
             self.stretch.close()
             self.resampler.close()
-            self._L.pv_pitch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != PV_OK:
-            raise PvError(rc, self._L.pv_pitch_last_error(self._h).decode())
+        super().close()
 
     @property
     def latency(self):
         """The output's lag in output samples: ((N - hs) + W) L / M."""
         return ((self.fft_size - self.synthesis_hop) + self.resampler.half_width) * self.resampler.up / self.resampler.down
-
-    def reset(self):
-        self._check(self._L.pv_pitch_reset(self._h))
-
-    def set_stream(self, hip_stream):
-        self._check(self._L.pv_pitch_set_stream(self._h, C.c_void_p(hip_stream)))
-
-    def synchronize(self):
-        self._check(self._L.pv_pitch_synchronize(self._h))
 
     def process(self, x):
         """x: float32[nch, nframes * analysis_hop] (host) -> float32[nch, resampler.out_count(nframes * synthesis_hop)]."""

@@ -17,17 +17,24 @@
 #include <immintrin.h>
 #endif
 
-#include "../../include/phaze_amd.h"
+#include "host/pv_host_common.h"
 #include "pv_kernels.h"
 
 namespace {
-constexpr uint32_t kMagic = 0x50564d49u;   // 'PVMI'
 constexpr int kHdrFloats = 16;             // pinned staging header: [0] = pitchFactor
 constexpr int kMaxPieces = 16;             // pieces a pipelined host-buffer batch is cut into at most
 constexpr int kFwdStatWords = 1024;        // forward-transform statistics: [0, 256) 128 x {frames, fallbacks} (pv_forward_stats); the rest belongs to the validation
                                            // build -DPV_FLIP_COUNT: [256, 512) 128 x {frames whose flags differ, of those not caught by the guard}, [512] largest q
-thread_local char g_create_err[256] = "";
 }  // namespace
+
+// The kernel family of a handle: decided once in pv_create (pick_family), every question about it answered by one family_* function below.
+enum Family {
+    kChain,      // any supported size: the generic chain kernel (pv_kernels.hip); N >= 16384 with scratch in device memory
+    kWave1k,     // N = 1024: wave-per-frame kernel (pv_wave_kernel.hip)
+    kWave2k,     // N = 2048, hop 128..2048: one wave per frame (pv_wave2k_kernel.hip)
+    kWg8,        // N = 2048..8192, R <= 8: register-resident workgroup kernel, eight elements per thread (pv_wg_kernel.hip)
+    kWg16,       // N = 4096 / 8192, hop N/8..N: sixteen elements per thread, N/32 threads per frame chain (pv_wg16_kernel.hip)
+};
 
 struct pv_handle {
     uint32_t magic;
@@ -67,7 +74,6 @@ struct pv_handle {
     unsigned *d_ctl;
     bool resident_bar;                           // the resident kernel's control block lives in DEVICE memory, written by the host through the BAR
     bool resident_in_bar;                        // ... and so does its input (largest quantum <= 16 KB; otherwise the waves read it from pinned host memory)
-    bool resident_wg;                            // the resident kernel is pv_wg_kernel: one control word per channel slot (ctl[16 + c]), channels handed over one by one
     bool copied[64];                             // pv_process_end: channels whose output has been copied out already
     bool resident_on;                            // a resident kernel has been launched on the stream and not been stopped since
     std::chrono::steady_clock::time_point last_quantum;   // ... and when it was last given work (its waves leave after ~50 ms without)
@@ -84,10 +90,7 @@ struct pv_handle {
     int64_t pending_time_cursor;
     bool host_channels;                          // PV_FLAG_HOST_CHANNEL_BOOKKEEPING: a changed nch resets nothing here
     bool test_fail_piece = false;      // PV_FLAG_TEST_FAIL_SECOND_PIECE: the second piece of a pipelined host-buffer batch reports a device error (exercises the roll-back)
-    bool use_wave;                               // N = 1024: wave-per-frame kernel (pv_wave_kernel.hip)
-    bool use_wg;                                 // N = 2048..8192, R <= 8: register-resident workgroup kernel (pv_wg_kernel.hip)
-    bool use_wave2k;                             // N = 2048, hop 128..2048: one wave per frame (pv_wave2k_kernel.hip)
-    bool use_wg16;                               // N = 4096 / 8192, hop N/8..N: sixteen elements per thread, N/32 threads per frame chain (pv_wg16_kernel.hip); implies use_wg
+    Family family;                               // which kernels run the frames (pick_family)
     char devname[64];
     char err[256];
 };
@@ -99,39 +102,163 @@ namespace {
 // (pv_get_time_cursor and the next output unchanged); the asynchronous pv_process_batch_device cannot know, its errors surface in pv_synchronize.
 struct Commit { int cur; int64_t time_cursor; int active_nch; };
 
-int fail(pv_handle *h, int code, const char *msg)
+PV_HOST_HANDLE(pv_handle, 0x50564d49u /* 'PVMI' */, pv_destroy);
+
+// ---- the kernel family: one function per question ----
+
+// Today's rules: the register-resident kernels where they exist; PV_FLAG_GENERIC_KERNEL and PV_FLAG_WORKGROUP_KERNEL are explicit A/B switches (tests,
+// measurements; no environment is read).  The sixteen-element and the one-wave kernel never meet in the product; the reference-width flavour's
+// sixteen-element kernel also takes N = 2048 and goes first.
+Family pick_family(int log2n, int hop, int32_t flags)
 {
-    if (h) snprintf(h->err, sizeof h->err, "%s", msg);
-    else snprintf(g_create_err, sizeof g_create_err, "%s", msg);
-    return code;
+    if (flags & PV_FLAG_GENERIC_KERNEL) return kChain;
+    if (pv_wave_supported(log2n, hop)) return kWave1k;
+    if (!pv_wg_supported(log2n, hop)) return kChain;
+    if (flags & PV_FLAG_WORKGROUP_KERNEL) return kWg8;                 // A/B: the eight-element workgroup kernel where a one-wave / sixteen-element kernel exists
+    return pv_wg16_supported(log2n, hop) ? kWg16 : pv_wave2k_supported(log2n, hop) ? kWave2k : kWg8;
 }
 
-int fail_hip(pv_handle *h, hipError_t e, const char *what)
+const char *family_kernel_name(Family f)
 {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return fail(h, PV_ERR_DEVICE, buf);
+    switch (f) {
+    case kWave1k: return "pv_wave_kernel_1024";
+    case kWave2k: return "pv_wave2k_kernel";
+    case kWg8: return "pv_wg_kernel";
+    case kWg16: return "pv_wg16_kernel";
+    case kChain: return "pv_chain_kernel";
+    }
+    return "";                                                         // (not reached: -Wswitch names a family without its case)
 }
 
-#define HIPCHK(h, call)                                            \
-    do {                                                           \
-        hipError_t e_ = (call);                                    \
-        if (e_ != hipSuccess) return fail_hip((h), e_, #call);     \
-    } while (0)
+int family_threads(const pv_handle *h)
+{
+    switch (h->family) {
+    case kWave1k: return pv_wave_threads();
+    case kWave2k: return pv_wave2k_threads();
+    case kWg8: case kWg16: return pv_wg_threads(h->log2n, h->hop, h->family == kWg8);
+    case kChain: return pv_kernel_threads(h->log2n);
+    }
+    return 0;
+}
 
-bool live(const pv_handle *h) { return h && h->magic == kMagic; }
+size_t family_lds_bytes(const pv_handle *h)
+{
+    switch (h->family) {
+    case kWave1k: return pv_wave_lds_bytes();
+    case kWave2k: return pv_wave2k_lds_bytes();
+    case kWg8: case kWg16: return pv_wg_lds_bytes(h->log2n, h->hop, h->family == kWg8);
+    case kChain: return pv_kernel_lds_bytes(h->log2n, h->hop);
+    }
+    return 0;
+}
+
+// Chains one CU runs concurrently (wave kernels: one per wave; others: LDS-limited workgroups per CU)
+long family_chains_per_cu(const pv_handle *h)
+{
+    long per_cu = 1;
+    switch (h->family) {
+    case kWave1k: return pv_wave_threads() / 64;
+    case kWave2k: return pv_wave2k_threads() / 64;
+    case kWg8: case kWg16: per_cu = (160 * 1024) / (long)(family_lds_bytes(h) + 256); break;         // (+ 256 static bytes: __syncthreads_or)
+    case kChain: per_cu = (160 * 1024) / (long)family_lds_bytes(h); if (per_cu > 8) per_cu = 8; break;
+    }
+    return per_cu < 1 ? 1 : per_cu;
+}
+
+// The two chain lists of an N = 1024 batch launch whose chain classes are sorted on the device: room for two lists of `chains` chains each (grown on demand)
+int next_chain_lists(pv_handle *h, long chains, unsigned **list, unsigned **list_next)
+{
+    if (chains > h->chain_list_cap) {
+        const long cap = chains + chains / 2 + 64;
+        const size_t words = 2 * (size_t)(2 + 2 * cap);
+        size_t held = 0;                                               // (regrown whatever it holds)
+        h->chain_list_cap = 0;
+        // TWO lists, used alternately: the classification of launch k zeroes the counters launch k + 1 will fill (the kernels of launch k - 1, which read them, are
+        // behind it in stream order), so no memset sits in front of every launch (round 6: 4.6 us of a 1.7 ms step)
+        const int rc = grow(h, &h->d_chain_list, &held, words);
+        if (rc != PV_OK) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_chain_list, 0, sizeof(unsigned) * words, h->stream));
+        h->chain_list_cap = cap;
+        h->chain_list_flip = 0;
+    }
+    *list = h->d_chain_list + (size_t)h->chain_list_flip * (size_t)(2 + 2 * h->chain_list_cap);
+    *list_next = h->d_chain_list + (size_t)(h->chain_list_flip ^ 1) * (size_t)(2 + 2 * h->chain_list_cap);
+    h->chain_list_flip ^= 1;
+    return PV_OK;
+}
+
+// The batch launch of nch channel slots x nchunks chains.  spread, dbg_ch: see launch_chain.
+int family_launch(pv_handle *h, PvKernelParams &p, int nch, int nchunks, int spread, int dbg_ch)
+{
+    const char *grid_y = "more than 65535 channel slots in one launch (grid.y limit): split the call";
+    hipError_t e = hipSuccess;
+    switch (h->family) {
+    case kWave2k:                                                    // (pv_debug_frame runs the tap instance of the kernel the handle uses)
+        e = pv_launch_wave2k(p, nch, nchunks, h->stream);
+        break;
+    case kWave1k: {
+        unsigned *list = nullptr, *list_next = nullptr;
+        if (spread < 0 && dbg_ch < 0) {
+            const int rc = next_chain_lists(h, (long)nch * nchunks, &list, &list_next);
+            if (rc != PV_OK) return rc;
+        }
+        e = pv_launch_wave(p, nch, nchunks, h->stream, spread, list, list_next);
+        break;
+    }
+    case kWg8: case kWg16:
+        if (nch > 65535) return fail(h, PV_ERR_CAPACITY, grid_y);
+        e = pv_launch_wg(h->log2n, p, nch, nchunks, h->stream, h->family == kWg8);
+        break;
+    case kChain: {
+        if (nch > 65535) return fail(h, PV_ERR_CAPACITY, grid_y);
+        // N >= 16384: the generic kernel keeps its fp32 buffer and its overlap-add ring (N = 32768: its fp64 buffer too) in device memory, one slice per workgroup
+        const size_t stride = pv_kernel_gscratch_bytes(h->log2n, h->hop);
+        if (stride) {
+            const size_t need = stride * (size_t)nch * (size_t)nchunks;
+            if (need > ((size_t)16 << 30)) return fail(h, PV_ERR_CAPACITY, "fft_size >= 16384: the launch needs more than 16 GiB of scratch (fewer channels or hops per call)");
+            const int rc = grow(h, &h->d_gscratch, &h->gscratch_cap, need);
+            if (rc != PV_OK) return rc;
+            p.gscratch = h->d_gscratch; p.gscratch_stride = stride;
+        }
+        e = pv_launch_chain(h->log2n, p, nch, nchunks, h->stream);
+        break;
+    }
+    }
+    if (e != hipSuccess) return fail_hip(h, e, "kernel launch");
+    return PV_OK;
+}
+
+// Does the family have a resident streaming form (PV_FLAG_PERSISTENT_STREAM) at this size?
+bool family_resident_supported(Family f, int log2n, int hop)
+{
+    switch (f) {
+    case kWave1k: case kWave2k: return true;
+    case kWg8: case kWg16: return pv_wg_resident_supported(log2n, hop, f == kWg8);
+    case kChain: return false;
+    }
+    return false;
+}
+
+// The resident workgroup kernels take one control word per channel slot (ctl[16 + c]): channels are handed over one by one
+bool family_resident_per_channel(Family f) { return f == kWg8 || f == kWg16; }
+
+hipError_t family_launch_resident(pv_handle *h, const PvKernelParams &p)
+{
+    switch (h->family) {
+    case kWave1k: return pv_launch_wave_resident(p, h->max_channels, h->stream);
+    case kWave2k: return pv_launch_wave2k_resident(p, h->max_channels, h->stream);
+    case kWg8: case kWg16: return pv_launch_wg_resident(h->log2n, p, h->max_channels, h->stream, h->family == kWg8);
+    case kChain: break;                                                // (no resident form: family_resident_supported)
+    }
+    return hipErrorNotSupported;
+}
 
 int pick_frames_per_chunk(const pv_handle *h, int nch, int nhops)
 {
     if (h->frames_per_chunk_cfg > 0) return h->frames_per_chunk_cfg;
     // Trade-off: long chains amortise the (R-1)-frame halo, but the last partial round of workgroups idles the chip.
-    // resident = chains the GPU runs concurrently (wave kernels: one per wave; others: LDS-limited workgroups per CU).
-    long per_cu;
-    if (h->use_wave2k) per_cu = pv_wave2k_threads() / 64;
-    else if (h->use_wave) per_cu = pv_wave_threads() / 64;
-    else if (h->use_wg) { per_cu = (160 * 1024) / (long)(pv_wg_lds_bytes(h->log2n, h->hop, !h->use_wg16) + 256); if (per_cu < 1) per_cu = 1; }   // (+ 256 static bytes: __syncthreads_or)
-    else { per_cu = (160 * 1024) / (long)pv_kernel_lds_bytes(h->log2n, h->hop); if (per_cu > 8) per_cu = 8; if (per_cu < 1) per_cu = 1; }
-    const long resident = per_cu * h->cus;
+    // resident = chains the GPU runs concurrently
+    const long resident = family_chains_per_cu(h) * h->cus;
     const int R = h->R;
     int best = R > 1 ? R : 1;
     double best_eff = -1.0;
@@ -185,53 +312,7 @@ int launch_chain(pv_handle *h, const float *d_in, float *d_out, int ch0, int nch
     if (dbg_ch >= 0) { p.dbg_X = h->d_dbgX; p.dbg_mag = h->d_dbgMag; p.dbg_flags = h->d_dbgFlags; p.dbg_Y = h->d_dbgY; p.dbg_ch = dbg_ch; p.dbg_frame = 0; }
     const int nchunks = (nhops + p.frames_per_chunk - 1) / p.frames_per_chunk;
     h->last_frames_per_chunk = p.frames_per_chunk;
-    hipError_t e = hipSuccess;
-    if (h->use_wave2k) {                                         // (pv_debug_frame runs the tap instance of the kernel the handle uses)
-        e = pv_launch_wave2k(p, nch, nchunks, h->stream);
-    } else {
-        if (!h->use_wave && nch > 65535) return fail(h, PV_ERR_CAPACITY, "more than 65535 channel slots in one launch (grid.y limit): split the call");
-        unsigned *list = nullptr, *list_next = nullptr;
-        if (h->use_wave && spread < 0 && dbg_ch < 0) {
-            // chain classes are sorted on the device: room for two lists of nch * nchunks chains (grown on demand; a launch in flight may still read the old one)
-            const long chains = (long)nch * nchunks;
-            if (chains > h->chain_list_cap) {
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                if (h->d_chain_list) (void)hipFree(h->d_chain_list);
-                h->d_chain_list = nullptr; h->chain_list_cap = 0;
-                const long cap = chains + chains / 2 + 64;
-                // TWO lists, used alternately: the classification of launch k zeroes the counters launch k + 1 will fill (the kernels of launch k - 1, which read them, are
-                // behind it in stream order), so no memset sits in front of every launch (round 6: 4.6 us of a 1.7 ms step)
-                HIPCHK(h, hipMalloc(&h->d_chain_list, 2 * sizeof(unsigned) * (size_t)(2 + 2 * cap)));
-                HIPCHK(h, hipMemsetAsync(h->d_chain_list, 0, 2 * sizeof(unsigned) * (size_t)(2 + 2 * cap), h->stream));
-                h->chain_list_cap = cap;
-                h->chain_list_flip = 0;
-            }
-            list = h->d_chain_list + (size_t)h->chain_list_flip * (size_t)(2 + 2 * h->chain_list_cap);
-            list_next = h->d_chain_list + (size_t)(h->chain_list_flip ^ 1) * (size_t)(2 + 2 * h->chain_list_cap);
-            h->chain_list_flip ^= 1;
-        }
-        if (!h->use_wave && !h->use_wg) {
-            // N >= 16384: the generic kernel keeps its fp32 buffer and its overlap-add ring (N = 32768: its fp64 buffer too) in device memory, one slice per workgroup
-            const size_t stride = pv_kernel_gscratch_bytes(h->log2n, h->hop);
-            if (stride) {
-                const size_t need = stride * (size_t)nch * (size_t)nchunks;
-                if (need > ((size_t)16 << 30)) return fail(h, PV_ERR_CAPACITY, "fft_size >= 16384: the launch needs more than 16 GiB of scratch (fewer channels or hops per call)");
-                if (need > h->gscratch_cap) {
-                    HIPCHK(h, hipStreamSynchronize(h->stream));
-                    if (h->d_gscratch) (void)hipFree(h->d_gscratch);
-                    h->d_gscratch = nullptr; h->gscratch_cap = 0;
-                    HIPCHK(h, hipMalloc(&h->d_gscratch, need));
-                    h->gscratch_cap = need;
-                }
-                p.gscratch = h->d_gscratch; p.gscratch_stride = stride;
-            }
-        }
-        e = h->use_wave ? pv_launch_wave(p, nch, nchunks, h->stream, spread, list, list_next)
-          : h->use_wg ? pv_launch_wg(h->log2n, p, nch, nchunks, h->stream, !h->use_wg16)
-                      : pv_launch_chain(h->log2n, p, nch, nchunks, h->stream);
-    }
-    if (e != hipSuccess) return fail_hip(h, e, "kernel launch");
-    return PV_OK;
+    return family_launch(h, p, nch, nchunks, spread, dbg_ch);
 }
 
 // What a completed pass over the slots [0, nch) x [nhops] hops commits: the ping-pong flip (slots outside the pass keep their state: copied
@@ -345,8 +426,7 @@ int resident_start(pv_handle *h, unsigned last_seq)
     resident_publish(h, h->h_ctl + 4, 0u);
     // stale completion words must not match a future 16-bit sequence number (a slot unused for exactly 65535 quanta)
     for (int c = 0; c < h->max_channels; c++) h->h_done[c] = 0u;
-    const hipError_t e = h->resident_wg ? pv_launch_wg_resident(h->log2n, p, h->max_channels, h->stream, !h->use_wg16)
-                       : h->use_wave2k ? pv_launch_wave2k_resident(p, h->max_channels, h->stream) : pv_launch_wave_resident(p, h->max_channels, h->stream);
+    const hipError_t e = family_launch_resident(h, p);
     if (e != hipSuccess) return fail_hip(h, e, "resident kernel launch");
     h->resident_on = true;
     h->last_frames_per_chunk = 1;
@@ -371,7 +451,7 @@ const char *pv_status_string(int status)
     }
 }
 
-const char *pv_last_error(const pv_handle *h) { return live(h) ? h->err : g_create_err; }
+const char *pv_last_error(const pv_handle *h) { return last_error(h); }
 
 int pv_abi_version(void) { return PV_ABI_VERSION; }
 
@@ -387,37 +467,35 @@ int pv_device_count(int32_t *out)
 
 int pv_create(const pv_config *cfg, pv_handle **out)
 {
-    if (!cfg || !out) return fail(nullptr, PV_ERR_ARGUMENT, "pv_create: null argument");
+    if (!cfg || !out) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_create: null argument");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(pv_config))
-        return fail(nullptr, PV_ERR_ARGUMENT, "pv_create: pv_config.struct_size does not match this library (start from PV_CONFIG_INIT; PV_ABI_VERSION mismatch?)");
-    if (cfg->flags & ~(int32_t)PV_FLAG_ALL) return fail(nullptr, PV_ERR_ARGUMENT, "pv_create: unknown bits in pv_config.flags");
+        return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_create: pv_config.struct_size does not match this library (start from PV_CONFIG_INIT; PV_ABI_VERSION mismatch?)");
+    if (cfg->flags & ~(int32_t)PV_FLAG_ALL) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_create: unknown bits in pv_config.flags");
     const int N = cfg->fft_size;                                 // the host passes 2048 for the reference default (phase-vocoder.js:6)
     const int hop = cfg->hop_size;                               // ... and 128 (ola-processor.js:3)
     if (N <= 1 || (N & (N - 1)) != 0)                            // bundle:6-7
-        return fail(nullptr, PV_ERR_FFT_SIZE, "FFT size must be a power of two and bigger than 1");
-    if (hop <= 0 || N % hop != 0) return fail(nullptr, PV_ERR_ARGUMENT, "hop_size must be positive and divide fft_size");
+        return fail(kNoHandle, PV_ERR_FFT_SIZE, "FFT size must be a power of two and bigger than 1");
+    if (hop <= 0 || N % hop != 0) return fail(kNoHandle, PV_ERR_ARGUMENT, "hop_size must be positive and divide fft_size");
     int log2n = 0;
     while ((1 << log2n) < N) log2n++;
-    if (log2n > 20) return fail(nullptr, PV_ERR_UNSUPPORTED, "fft_size must be within 2..1048576 for the gfx950 kernels");
-    if (hop < 2) return fail(nullptr, PV_ERR_UNSUPPORTED, "hop_size must be >= 2");
-    {
-        const bool generic = (cfg->flags & PV_FLAG_GENERIC_KERNEL) != 0;
-        const bool reg_kernel = !generic && (pv_wave_supported(log2n, hop) || pv_wg_supported(log2n, hop));
-        if (!reg_kernel && pv_kernel_lds_bytes(log2n, hop) > 160 * 1024 - 512)
-            return fail(nullptr, PV_ERR_UNSUPPORTED, "fft_size/hop_size combination exceeds the 160 KiB LDS of a CU");
-    }
+    if (log2n > 20) return fail(kNoHandle, PV_ERR_UNSUPPORTED, "fft_size must be within 2..1048576 for the gfx950 kernels");
+    if (hop < 2) return fail(kNoHandle, PV_ERR_UNSUPPORTED, "hop_size must be >= 2");
+    const Family family = pick_family(log2n, hop, cfg->flags);
+    if (family == kChain && pv_kernel_lds_bytes(log2n, hop) > 160 * 1024 - 512)
+        return fail(kNoHandle, PV_ERR_UNSUPPORTED, "fft_size/hop_size combination exceeds the 160 KiB LDS of a CU");
     const int maxch = cfg->max_channels > 0 ? cfg->max_channels : 2;
     const int maxhops = cfg->max_hops > 0 ? cfg->max_hops : 1;
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return fail(nullptr, PV_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, PV_ERR_ARGUMENT, "device_id out of range");
+    if (e != hipSuccess || ndev <= 0) return fail(kNoHandle, PV_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(kNoHandle, PV_ERR_ARGUMENT, "device_id out of range");
 
     pv_handle *h = (pv_handle *)calloc(1, sizeof(pv_handle));
-    if (!h) return fail(nullptr, PV_ERR_DEVICE, "pv_create: out of host memory");
-    h->magic = kMagic;
+    if (!h) return fail(kNoHandle, PV_ERR_DEVICE, "pv_create: out of host memory");
+    h->magic = HostTraits<pv_handle>::kMagic;
+    h->family = family;
     h->N = N; h->hop = hop; h->L = N - hop; h->R = N / hop; h->log2n = log2n;
     h->max_channels = maxch; h->max_hops = maxhops; h->device = cfg->device_id;
     h->frames_per_chunk_cfg = cfg->frames_per_chunk;
@@ -432,70 +510,32 @@ int pv_create(const pv_config *cfg, pv_handle **out)
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device_id) != hipSuccess || khz <= 0) { (void)hipGetLastError(); khz = 100000; }
         h->idle_ticks = (unsigned)khz * 50u;
     }
-    {
-        const bool generic = (cfg->flags & PV_FLAG_GENERIC_KERNEL) != 0;      // explicit A/B switch (tests, measurements); no environment is read
-        h->use_wave = pv_wave_supported(log2n, hop) && !generic;
-        h->use_wg = pv_wg_supported(log2n, hop) && !generic;
-        const bool wg_only = (cfg->flags & PV_FLAG_WORKGROUP_KERNEL) != 0;    // A/B: the eight-element workgroup kernel where a one-wave / sixteen-element kernel exists
-        h->use_wg16 = h->use_wg && !wg_only && pv_wg16_supported(log2n, hop);
-        h->use_wave2k = h->use_wg && !wg_only && !h->use_wg16 && pv_wave2k_supported(log2n, hop);   // (the two never meet in the product; the reference-width flavour's sixteen-element kernel also takes N = 2048)
-    }
 
-#define CHK(call)                                                          \
-    do {                                                                   \
-        hipError_t e2_ = (call);                                           \
-        if (e2_ != hipSuccess) {                                           \
-            int rc_ = fail_hip(nullptr, e2_, #call);                       \
-            pv_destroy(h);                                                 \
-            return rc_;                                                    \
-        }                                                                  \
-    } while (0)
-    CHK(hipSetDevice(h->device));
+    CREATE_CHK(h, hipSetDevice(h->device));
     hipDeviceProp_t prop;
-    CHK(hipGetDeviceProperties(&prop, h->device));
+    CREATE_CHK(h, hipGetDeviceProperties(&prop, h->device));
     h->cus = prop.multiProcessorCount;
     snprintf(h->devname, sizeof h->devname, "%s (%s)", prop.name[0] ? prop.name : "AMD GPU", prop.gcnArchName);
-    CHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    CREATE_CHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
 
-    // tables: twiddles exp(-2 pi j k/N) (role of bundle:12-18) and the periodic Hann window (pv:8-14), fp64 on host
-    std::vector<double2> tw64(N);
-    std::vector<float2> tw32(N);
-    std::vector<float> hann(N);
-    for (int k = 0; k < N; k++) {
-        const double ang = 2.0 * M_PI * (double)k / (double)N;
-        tw64[k] = double2{cos(ang), -sin(ang)};
-        tw32[k] = float2{(float)tw64[k].x, (float)tw64[k].y};
-        hann[k] = (float)(0.5 * (1.0 - cos(ang)));
-    }
-    // exact values on the axes (libm returns ~1e-16 residues)
-    tw64[0] = double2{1, 0}; tw32[0] = float2{1, 0};
-    if (N >= 4) { tw64[N / 4] = double2{0, -1}; tw32[N / 4] = float2{0, -1}; tw64[3 * N / 4] = double2{0, 1}; tw32[3 * N / 4] = float2{0, 1}; }
-    tw64[N / 2] = double2{-1, 0}; tw32[N / 2] = float2{-1, 0};
-    CHK(hipMalloc(&h->d_tw64, sizeof(double2) * N));
-    CHK(hipMalloc(&h->d_tw32, sizeof(float2) * N));
-    CHK(hipMalloc(&h->d_hann, sizeof(float) * 2 * N));                       // [0, N): the window; [N, 2N): half of it (exact), for kernels that fold the 1/2 of the split pass into it
-    CHK(hipMemcpy(h->d_tw64, tw64.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
-    CHK(hipMemcpy(h->d_tw32, tw32.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-    CHK(hipMemcpy(h->d_hann, hann.data(), sizeof(float) * N, hipMemcpyHostToDevice));
-    for (int k = 0; k < N; k++) hann[k] *= 0.5f;
-    CHK(hipMemcpy(h->d_hann + N, hann.data(), sizeof(float) * N, hipMemcpyHostToDevice));
+    CREATE_CHK(h, upload_tables(N, true, &h->d_tw64, &h->d_tw32, &h->d_hann));            // d_hann: [0, N) the window, [N, 2N) half of it
 
-    CHK(hipMalloc(&h->d_fwd_stats, sizeof(unsigned long long) * kFwdStatWords));
-    CHK(hipMemset(h->d_fwd_stats, 0, sizeof(unsigned long long) * kFwdStatWords));
+    CREATE_CHK(h, hipMalloc(&h->d_fwd_stats, sizeof(unsigned long long) * kFwdStatWords));
+    CREATE_CHK(h, hipMemset(h->d_fwd_stats, 0, sizeof(unsigned long long) * kFwdStatWords));
     const size_t state = sizeof(float) * (size_t)maxch * (size_t)(h->L > 0 ? h->L : 1);
     for (int i = 0; i < 2; i++) {
-        CHK(hipMalloc(&h->d_hist[i], state));
-        CHK(hipMalloc(&h->d_acc[i], state));
-        CHK(hipMemset(h->d_hist[i], 0, state));
-        CHK(hipMemset(h->d_acc[i], 0, state));
+        CREATE_CHK(h, hipMalloc(&h->d_hist[i], state));
+        CREATE_CHK(h, hipMalloc(&h->d_acc[i], state));
+        CREATE_CHK(h, hipMemset(h->d_hist[i], 0, state));
+        CREATE_CHK(h, hipMemset(h->d_acc[i], 0, state));
     }
     const size_t stage = sizeof(float) * (size_t)maxch * (size_t)maxhops * (size_t)hop;
-    CHK(hipMalloc(&h->d_stage_in, stage));
-    CHK(hipMalloc(&h->d_stage_out, stage));
-    CHK(hipMalloc(&h->d_pitch, sizeof(float) * (size_t)maxch * (size_t)maxhops));
+    CREATE_CHK(h, hipMalloc(&h->d_stage_in, stage));
+    CREATE_CHK(h, hipMalloc(&h->d_stage_out, stage));
+    CREATE_CHK(h, hipMalloc(&h->d_pitch, sizeof(float) * (size_t)maxch * (size_t)maxhops));
     const size_t quantum = sizeof(float) * (kHdrFloats + 2 * (size_t)maxch * hop);
-    CHK(hipHostMalloc((void **)&h->h_pin, quantum, hipHostMallocMapped));
+    CREATE_CHK(h, hipHostMalloc((void **)&h->h_pin, quantum, hipHostMallocMapped));
     {
         // streaming quantum: the kernel reads the hop straight from / writes it straight to pinned host memory (one launch + one sync,
         // no copy nodes).  PV_FLAG_STREAM_COPY restores H2D + kernel + D2H staging.
@@ -503,7 +543,7 @@ int pv_create(const pv_config *cfg, pv_handle **out)
         if (!(cfg->flags & PV_FLAG_STREAM_COPY) && hipHostGetDevicePointer(&dp, h->h_pin, 0) == hipSuccess) h->d_pin_mapped = (float *)dp;
         (void)hipGetLastError();
     }
-    CHK(hipMalloc(&h->d_quantum, quantum));
+    CREATE_CHK(h, hipMalloc(&h->d_quantum, quantum));
     {
         int large_bar = 0;
         if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) { large_bar = 0; (void)hipGetLastError(); }
@@ -525,30 +565,29 @@ int pv_create(const pv_config *cfg, pv_handle **out)
         // completion words of the streaming quantum, one per channel slot, in pinned host memory the kernels store to
         unsigned *hd = nullptr;
         void *dd = nullptr;
-        CHK(hipHostMalloc((void **)&hd, sizeof(unsigned) * (size_t)maxch, hipHostMallocMapped));
+        CREATE_CHK(h, hipHostMalloc((void **)&hd, sizeof(unsigned) * (size_t)maxch, hipHostMallocMapped));
         memset(hd, 0, sizeof(unsigned) * (size_t)maxch);
         h->h_done = hd;
         if (hipHostGetDevicePointer(&dd, hd, 0) == hipSuccess) h->d_done = (unsigned *)dd;
         (void)hipGetLastError();
         if (h->d_done && (cfg->flags & PV_FLAG_PERSISTENT_STREAM) && maxch <= 64 &&
-            (h->use_wave || h->use_wave2k || (h->use_wg && pv_wg_resident_supported(log2n, hop, !h->use_wg16)))) {
+            family_resident_supported(family, log2n, hop)) {
             // Control block: in DEVICE memory when the host can write it through the BAR and the largest quantum is small enough to travel the same
             // way -- the waves then poll their own HBM and find the input there too, the only PCIe traffic of a quantum being posted writes in both
             // directions (tools/bar_probe.hip: 1 KB handed over and acknowledged in 3.5 us, 7.2 us with the block and the input in pinned host memory)
-            h->resident_wg = !(h->use_wave || h->use_wave2k);
             h->resident_bar = h->bar_input;
             h->resident_in_bar = h->bar_input && sizeof(float) * (size_t)maxch * hop <= 16384;
-            constexpr size_t kCtlBytes = sizeof(unsigned) * (16 + 64);       // {seq word, -, -, -, stop, slots in use, ...} + one word per channel slot (resident_wg)
+            constexpr size_t kCtlBytes = sizeof(unsigned) * (16 + 64);       // {seq word, -, -, -, stop, slots in use, ...} + one word per channel slot (family_resident_per_channel)
             if (h->resident_bar) {
                 void *dc = nullptr;
-                CHK(hipMalloc(&dc, kCtlBytes));
-                CHK(hipMemset(dc, 0, kCtlBytes));
+                CREATE_CHK(h, hipMalloc(&dc, kCtlBytes));
+                CREATE_CHK(h, hipMemset(dc, 0, kCtlBytes));
                 h->d_ctl = (unsigned *)dc;
                 h->h_ctl = (volatile unsigned *)dc;                          // (written, never read, by the host)
             } else {
                 unsigned *hc = nullptr;
                 void *dc = nullptr;
-                CHK(hipHostMalloc((void **)&hc, kCtlBytes, hipHostMallocMapped));
+                CREATE_CHK(h, hipHostMalloc((void **)&hc, kCtlBytes, hipHostMallocMapped));
                 memset(hc, 0, kCtlBytes);
                 h->h_ctl = hc;
                 if (hipHostGetDevicePointer(&dc, hc, 0) == hipSuccess) h->d_ctl = (unsigned *)dc; else h->h_ctl = nullptr;
@@ -556,15 +595,14 @@ int pv_create(const pv_config *cfg, pv_handle **out)
             }
         }
     }
-    CHK(hipMalloc(&h->d_dbgX, sizeof(double) * 2 * N));
-    CHK(hipMalloc(&h->d_dbgMag, sizeof(float) * (N / 2 + 1)));
-    CHK(hipMalloc(&h->d_dbgFlags, sizeof(int) * (N / 2 + 1)));
-    CHK(hipMalloc(&h->d_dbgY, sizeof(float) * 2 * (N / 2 + 1)));
+    CREATE_CHK(h, hipMalloc(&h->d_dbgX, sizeof(double) * 2 * N));
+    CREATE_CHK(h, hipMalloc(&h->d_dbgMag, sizeof(float) * (N / 2 + 1)));
+    CREATE_CHK(h, hipMalloc(&h->d_dbgFlags, sizeof(int) * (N / 2 + 1)));
+    CREATE_CHK(h, hipMalloc(&h->d_dbgY, sizeof(float) * 2 * (N / 2 + 1)));
 #ifdef PV_STAMPS
-    CHK(hipMalloc(&h->d_stamps, sizeof(unsigned) * 16 * 65536));
-    CHK(hipMemset(h->d_stamps, 0, sizeof(unsigned) * 16 * 65536));
+    CREATE_CHK(h, hipMalloc(&h->d_stamps, sizeof(unsigned) * 16 * 65536));
+    CREATE_CHK(h, hipMemset(h->d_stamps, 0, sizeof(unsigned) * 16 * 65536));
 #endif
-#undef CHK
     *out = h;
     return PV_OK;
 }
@@ -572,7 +610,7 @@ int pv_create(const pv_config *cfg, pv_handle **out)
 int pv_destroy(pv_handle *h)
 {
     if (!h) return PV_OK;
-    if (h->magic != kMagic) return PV_ERR_DESTROYED;
+    if (!live(h)) return PV_ERR_DESTROYED;
     (void)hipSetDevice(h->device);
     (void)resident_stop(h);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
@@ -606,11 +644,9 @@ int pv_get_info(const pv_handle *h, pv_info *out)
     memset(out, 0, sizeof *out);
     out->fft_size = h->N; out->hop_size = h->hop; out->overlaps = h->R;
     out->max_channels = h->max_channels; out->max_hops = h->max_hops;
-    out->threads_per_workgroup = h->use_wave ? pv_wave_threads() : h->use_wave2k ? pv_wave2k_threads() : h->use_wg ? pv_wg_threads(h->log2n, h->hop, !h->use_wg16) : pv_kernel_threads(h->log2n);
-    snprintf(out->kernel_name, sizeof out->kernel_name, "%s",
-             h->use_wave ? "pv_wave_kernel_1024" : h->use_wave2k ? "pv_wave2k_kernel" : h->use_wg16 ? "pv_wg16_kernel" : h->use_wg ? "pv_wg_kernel" : "pv_chain_kernel");
-    out->lds_bytes_per_workgroup = (int32_t)(h->use_wave ? pv_wave_lds_bytes() : h->use_wave2k ? pv_wave2k_lds_bytes()
-                                             : h->use_wg ? pv_wg_lds_bytes(h->log2n, h->hop, !h->use_wg16) : pv_kernel_lds_bytes(h->log2n, h->hop));
+    out->threads_per_workgroup = family_threads(h);
+    snprintf(out->kernel_name, sizeof out->kernel_name, "%s", family_kernel_name(h->family));
+    out->lds_bytes_per_workgroup = (int32_t)family_lds_bytes(h);
     out->frames_per_chunk = h->last_frames_per_chunk;
     out->compute_units = h->cus; out->device_id = h->device;
     snprintf(out->device_name, sizeof out->device_name, "%s", h->devname);
@@ -786,7 +822,7 @@ int pv_process_begin(pv_handle *h, const float *const *in, int32_t nch, int32_t 
         if (paused || !in[c]) memset(pin_in + (size_t)c * hop, 0, sizeof(float) * hop);
         else memcpy(pin_in + (size_t)c * hop, in[c], sizeof(float) * hop);       // host block is only valid during the call (ola:64)
     };
-    const bool piecewise = h->h_ctl && h->resident_wg && h->d_pin_mapped;       // resident workgroup kernel: every channel is handed over as soon as it is staged
+    const bool piecewise = h->h_ctl && family_resident_per_channel(h->family) && h->d_pin_mapped;       // resident workgroup kernel: every channel is handed over as soon as it is staged
     if (!piecewise) for (int c = 0; c < nch; c++) stage_channel(c);
 #if defined(__x86_64__)
     if (bar) _mm_sfence();                                                       // write-combining buffers drained before the doorbell
@@ -1003,12 +1039,8 @@ int pv_process_batch(pv_handle *h, const float *in, float *out, int32_t nch, int
             // taken before the first piece, is what a failure in a later piece is rolled back to
             const int used = nch > h->used_channels ? nch : h->used_channels;
             const size_t fl = (size_t)used * (size_t)(h->L > 0 ? h->L : 1);
-            if (2 * fl > h->snap_floats) {
-                if (h->d_snap) (void)hipFree(h->d_snap);
-                h->d_snap = nullptr; h->snap_floats = 0;
-                HIPCHK(h, hipMalloc(&h->d_snap, 2 * fl * sizeof(float)));
-                h->snap_floats = 2 * fl;
-            }
+            const int rg = grow(h, &h->d_snap, &h->snap_floats, 2 * fl);
+            if (rg != PV_OK) return rg;
             HIPCHK(h, hipMemcpyAsync(h->d_snap, h->d_hist[h->cur], fl * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(h->d_snap + fl, h->d_acc[h->cur], fl * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             snap_fl = fl;
@@ -1058,7 +1090,7 @@ int pv_host_alloc(size_t bytes, void **out)
     if (bytes == 0) return PV_ERR_ARGUMENT;
     void *p = nullptr;
     const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocPortable);        // visible to every device of the process
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail_hip(nullptr, e, "pv_host_alloc: hipHostMalloc"); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail_hip(kNoHandle, e, "pv_host_alloc: hipHostMalloc"); }
     *out = p;
     return PV_OK;
 }
@@ -1067,7 +1099,7 @@ int pv_host_free(void *p)
 {
     if (!p) return PV_OK;
     const hipError_t e = hipHostFree(p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail_hip(nullptr, e, "pv_host_free: hipHostFree"); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail_hip(kNoHandle, e, "pv_host_free: hipHostFree"); }
     return PV_OK;
 }
 

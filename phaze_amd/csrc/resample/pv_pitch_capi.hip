@@ -9,12 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../../include/phaze_amd.h"
-
-namespace {
-constexpr uint32_t kPitchMagic = 0x50565054u;   // 'PVPT'
-thread_local char g_pitch_create_err[384] = "";
-}  // namespace
+#include "../host/pv_host_common.h"
 
 struct pv_pitch {
     uint32_t magic;
@@ -29,58 +24,30 @@ struct pv_pitch {
 
 namespace {
 
-int pfail(pv_pitch *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof h->err, "%s", msg);
-    else snprintf(g_pitch_create_err, sizeof g_pitch_create_err, "%s", msg);
-    return code;
-}
-
-bool plive(const pv_pitch *h) { return h && h->magic == kPitchMagic; }
-
-int grow(pv_pitch *h, float **buf, size_t *cap, size_t words)
-{
-    if (words <= *cap) return PV_OK;
-    hipError_t e = hipStreamSynchronize(h->stream);                    // a launch in flight may still use the old buffer
-    if (e == hipSuccess && *buf) e = hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    if (e == hipSuccess) e = hipMalloc(buf, words * sizeof(float));
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "pv_pitch: device buffer of %zu floats: %s", words, hipGetErrorString(e));
-        return pfail(h, PV_ERR_DEVICE, msg);
-    }
-    *cap = words;
-    return PV_OK;
-}
+PV_HOST_HANDLE(pv_pitch, 0x50565054u /* 'PVPT' */, pv_pitch_destroy);
 
 // Device pointers, asynchronous on h->stream.  The stretch validates its own arguments (and rejects with its state untouched) before the resampler moves.
 int run(pv_pitch *h, const char *fn, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
         const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride, int64_t out_capacity, int64_t *nout)
 {
-    char msg[384];
-    if (nch < 0 || nframes < 0) { snprintf(msg, sizeof msg, "%s: negative channel or frame count", fn); return pfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return pfail(h, PV_ERR_CAPACITY, msg); }
+    if (nch < 0 || nframes < 0) return failf(h, PV_ERR_ARGUMENT, "%s: negative channel or frame count", fn);
+    if (nch > h->max_channels) return failf(h, PV_ERR_CAPACITY, "%s: more channels than max_channels", fn);
     const int64_t mid = (int64_t)nframes * h->hs;
     int64_t total = 0;
     (void)pv_resample_out_count(h->resample, mid, &total);
     if (nout) *nout = total;
-    if (out_capacity < total) {
-        snprintf(msg, sizeof msg, "%s: out_capacity %lld is below the %lld samples per channel this call produces", fn, (long long)out_capacity, (long long)total);
-        return pfail(h, PV_ERR_ARGUMENT, msg);
-    }
-    if (nch > 1 && out_stride < total) {
-        snprintf(msg, sizeof msg, "%s: out_stride shorter than the samples produced (%lld)", fn, (long long)total);
-        return pfail(h, PV_ERR_ARGUMENT, msg);
-    }
-    if (total > 0 && !d_out) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return pfail(h, PV_ERR_ARGUMENT, msg); }
+    if (out_capacity < total)
+        return failf(h, PV_ERR_ARGUMENT, "%s: out_capacity %lld is below the %lld samples per channel this call produces", fn, (long long)out_capacity,
+                     (long long)total);
+    if (nch > 1 && out_stride < total) return failf(h, PV_ERR_ARGUMENT, "%s: out_stride shorter than the samples produced (%lld)", fn, (long long)total);
+    if (total > 0 && !d_out) return failf(h, PV_ERR_ARGUMENT, "%s: null buffer", fn);
     if (nch == 0 || nframes == 0) return PV_OK;
     int rc = grow(h, &h->d_mid, &h->mid_cap, (size_t)nch * (size_t)mid);
     if (rc != PV_OK) return rc;
     rc = pv_transient_process_device(h->stretch, d_in, h->d_mid, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, mid);
-    if (rc != PV_OK) { snprintf(msg, sizeof msg, "%s: %s", fn, pv_stretch_last_error(h->stretch)); return pfail(h, rc, msg); }
+    if (rc != PV_OK) return failf(h, rc, "%s: %s", fn, pv_stretch_last_error(h->stretch));
     rc = pv_resample_process_device(h->resample, h->d_mid, nch, mid, mid, d_out, out_stride, out_capacity, nullptr);
-    if (rc != PV_OK) { snprintf(msg, sizeof msg, "%s: %s", fn, pv_resample_last_error(h->resample)); return pfail(h, rc, msg); }
+    if (rc != PV_OK) return failf(h, rc, "%s: %s", fn, pv_resample_last_error(h->resample));
     return PV_OK;
 }
 
@@ -88,12 +55,12 @@ int run(pv_pitch *h, const char *fn, const float *d_in, float *d_out, int32_t nc
 
 extern "C" {
 
-const char *pv_pitch_last_error(const pv_pitch *h) { return plive(h) ? h->err : g_pitch_create_err; }
+const char *pv_pitch_last_error(const pv_pitch *h) { return last_error(h); }
 
 int pv_pitch_destroy(pv_pitch *h)
 {
     if (!h) return PV_ERR_ARGUMENT;
-    if (!plive(h)) return PV_ERR_DESTROYED;
+    if (!live(h)) return PV_ERR_DESTROYED;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stretch) (void)pv_stretch_destroy(h->stretch);
     if (h->resample) (void)pv_resample_destroy(h->resample);
@@ -109,31 +76,31 @@ int pv_pitch_destroy(pv_pitch *h)
 
 int pv_pitch_create(const pv_pitch_config *cfg, pv_pitch **out)
 {
-    if (!cfg || !out) return pfail(nullptr, PV_ERR_ARGUMENT, "pv_pitch_create: null argument");
+    if (!cfg || !out) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_pitch_create: null argument");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(pv_pitch_config))
-        return pfail(nullptr, PV_ERR_ARGUMENT, "pv_pitch_create: pv_pitch_config.struct_size does not match this library (start from PV_PITCH_CONFIG_INIT)");
-    if (cfg->flags != 0) return pfail(nullptr, PV_ERR_ARGUMENT, "pv_pitch_create: unknown bits in pv_pitch_config.flags (must be 0)");
+        return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_pitch_create: pv_pitch_config.struct_size does not match this library (start from PV_PITCH_CONFIG_INIT)");
+    if (cfg->flags != 0) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_pitch_create: unknown bits in pv_pitch_config.flags (must be 0)");
     int32_t up = cfg->up, down = cfg->down;
     if (up == 0 && down == 0) { up = cfg->analysis_hop; down = cfg->synthesis_hop; }     // constant duration: pitch x hs / ha
     if (pv_resample_count(up, down, 0) < 0)
-        return pfail(nullptr, PV_ERR_ARGUMENT, "pv_pitch_create: up / down (0 / 0: analysis_hop / synthesis_hop) must be positive, within [1/8, 8], terms <= 8192 once reduced");
+        return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_pitch_create: up / down (0 / 0: analysis_hop / synthesis_hop) must be positive, within [1/8, 8], terms <= 8192 once reduced");
 
     pv_stretch_config sc = PV_STRETCH_CONFIG_INIT;
     sc.fft_size = cfg->fft_size; sc.analysis_hop = cfg->analysis_hop; sc.synthesis_hop = cfg->synthesis_hop;
     sc.max_channels = cfg->max_channels; sc.max_frames = 1; sc.device_id = cfg->device_id;
     pv_stretch *st = nullptr;
     int rc = pv_stretch_create(&sc, &st);
-    if (rc != PV_OK) return pfail(nullptr, rc, pv_stretch_last_error(nullptr));
+    if (rc != PV_OK) return fail(kNoHandle, rc, pv_stretch_last_error(nullptr));
     pv_resample_config rcfg = PV_RESAMPLE_CONFIG_INIT;
     rcfg.up = up; rcfg.down = down; rcfg.max_channels = cfg->max_channels; rcfg.max_samples = 1; rcfg.device_id = cfg->device_id;
     pv_resample *rs = nullptr;
     rc = pv_resample_create(&rcfg, &rs);
-    if (rc != PV_OK) { (void)pv_stretch_destroy(st); return pfail(nullptr, rc, pv_resample_last_error(nullptr)); }
+    if (rc != PV_OK) { (void)pv_stretch_destroy(st); return fail(kNoHandle, rc, pv_resample_last_error(nullptr)); }
 
     pv_pitch *h = (pv_pitch *)calloc(1, sizeof(pv_pitch));
-    if (!h) { (void)pv_stretch_destroy(st); (void)pv_resample_destroy(rs); return pfail(nullptr, PV_ERR_DEVICE, "pv_pitch_create: out of host memory"); }
-    h->magic = kPitchMagic;
+    if (!h) { (void)pv_stretch_destroy(st); (void)pv_resample_destroy(rs); return fail(kNoHandle, PV_ERR_DEVICE, "pv_pitch_create: out of host memory"); }
+    h->magic = HostTraits<pv_pitch>::kMagic;
     h->N = cfg->fft_size; h->ha = cfg->analysis_hop; h->hs = cfg->synthesis_hop;
     h->max_channels = cfg->max_channels > 0 ? cfg->max_channels : 1;
     h->device = cfg->device_id;
@@ -145,68 +112,62 @@ int pv_pitch_create(const pv_pitch_config *cfg, pv_pitch **out)
         e = hipMalloc(&h->d_mid, words * sizeof(float));
         if (e == hipSuccess) h->mid_cap = words;
     }
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "pv_pitch_create: %s", hipGetErrorString(e));
-        (void)pv_pitch_destroy(h);
-        return pfail(nullptr, PV_ERR_DEVICE, msg);
-    }
+    if (e != hipSuccess) { (void)pv_pitch_destroy(h); return failf(kNoHandle, PV_ERR_DEVICE, "pv_pitch_create: %s", hipGetErrorString(e)); }
     rc = pv_pitch_set_stream(h, nullptr);
-    if (rc != PV_OK) { snprintf(g_pitch_create_err, sizeof g_pitch_create_err, "%s", h->err); (void)pv_pitch_destroy(h); return rc; }
+    if (rc != PV_OK) { fail(kNoHandle, rc, h->err); (void)pv_pitch_destroy(h); return rc; }
     *out = h;
     return PV_OK;
 }
 
 int pv_pitch_reset(pv_pitch *h)
 {
-    if (!plive(h)) return PV_ERR_ARGUMENT;
+    if (!live(h)) return PV_ERR_ARGUMENT;
     int rc = pv_stretch_reset(h->stretch);
-    if (rc != PV_OK) return pfail(h, rc, pv_stretch_last_error(h->stretch));
+    if (rc != PV_OK) return fail(h, rc, pv_stretch_last_error(h->stretch));
     rc = pv_resample_reset(h->resample);
-    if (rc != PV_OK) return pfail(h, rc, pv_resample_last_error(h->resample));
+    if (rc != PV_OK) return fail(h, rc, pv_resample_last_error(h->resample));
     return PV_OK;
 }
 
 // Both inner handles run on ONE stream: the caller's, or the pitch handle's own
 int pv_pitch_set_stream(pv_pitch *h, void *hip_stream)
 {
-    if (!plive(h)) return PV_ERR_ARGUMENT;
+    if (!live(h)) return PV_ERR_ARGUMENT;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
-    if (h->stream && hipStreamSynchronize(h->stream) != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_set_stream: hipStreamSynchronize failed");
+    if (h->stream && hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_set_stream: hipStreamSynchronize failed");
     int rc = pv_stretch_set_stream(h->stretch, s);
-    if (rc != PV_OK) return pfail(h, rc, pv_stretch_last_error(h->stretch));
+    if (rc != PV_OK) return fail(h, rc, pv_stretch_last_error(h->stretch));
     rc = pv_resample_set_stream(h->resample, s);
-    if (rc != PV_OK) return pfail(h, rc, pv_resample_last_error(h->resample));
+    if (rc != PV_OK) return fail(h, rc, pv_resample_last_error(h->resample));
     h->stream = s;
     return PV_OK;
 }
 
 int pv_pitch_synchronize(pv_pitch *h)
 {
-    if (!plive(h)) return PV_ERR_ARGUMENT;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_synchronize: hipStreamSynchronize failed");
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_synchronize: hipStreamSynchronize failed");
     return PV_OK;
 }
 
-pv_stretch *pv_pitch_stretch(pv_pitch *h) { return plive(h) ? h->stretch : nullptr; }
-pv_resample *pv_pitch_resampler(pv_pitch *h) { return plive(h) ? h->resample : nullptr; }
+pv_stretch *pv_pitch_stretch(pv_pitch *h) { return live(h) ? h->stretch : nullptr; }
+pv_resample *pv_pitch_resampler(pv_pitch *h) { return live(h) ? h->resample : nullptr; }
 
 int pv_pitch_process_device(pv_pitch *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride,
                             const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride, int64_t out_capacity, int64_t *nout)
 {
-    if (!plive(h)) return PV_ERR_ARGUMENT;
-    if (hipSetDevice(h->device) != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_process_device: hipSetDevice failed");
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_process_device: hipSetDevice failed");
     return run(h, "pv_pitch_process_device", d_in, d_out, nch, nframes, hops, hop_stride, resets, reset_stride, in_stride, out_stride, out_capacity, nout);
 }
 
 int pv_pitch_process(pv_pitch *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, int64_t hop_stride, const uint8_t *resets,
                      int64_t reset_stride, int64_t in_stride, int64_t out_stride, int64_t out_capacity, int64_t *nout)
 {
-    if (!plive(h)) return PV_ERR_ARGUMENT;
-    char msg[256];
-    if (nch < 0 || nframes < 0) return pfail(h, PV_ERR_ARGUMENT, "pv_pitch_process: negative channel or frame count");
-    if (nch > h->max_channels) return pfail(h, PV_ERR_CAPACITY, "pv_pitch_process: more channels than max_channels");
-    if (hops && hop_stride != 0 && hop_stride < nframes) return pfail(h, PV_ERR_ARGUMENT, "pv_pitch_process: hop_stride is neither 0 nor >= nframes");
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    if (nch < 0 || nframes < 0) return fail(h, PV_ERR_ARGUMENT, "pv_pitch_process: negative channel or frame count");
+    if (nch > h->max_channels) return fail(h, PV_ERR_CAPACITY, "pv_pitch_process: more channels than max_channels");
+    if (hops && hop_stride != 0 && hop_stride < nframes) return fail(h, PV_ERR_ARGUMENT, "pv_pitch_process: hop_stride is neither 0 nor >= nframes");
     // the input each channel brings: its schedule row's total (the stretch checks the hops themselves; here they only must not overflow the sum)
     int64_t most = (int64_t)nframes * h->ha;
     if (hops) {
@@ -215,10 +176,8 @@ int pv_pitch_process(pv_pitch *h, const float *in, float *out, int32_t nch, int3
             int64_t t = 0;
             for (int m = 0; m < nframes; m++) {
                 const int32_t v = hops[(size_t)r * (size_t)hop_stride + m];
-                if (v < 1 || v > h->N) {
-                    snprintf(msg, sizeof msg, "pv_pitch_process: hop %d of channel %d, frame %d is outside [1, fft_size %d]", (int)v, r, m, h->N);
-                    return pfail(h, PV_ERR_ARGUMENT, msg);
-                }
+                if (v < 1 || v > h->N)
+                    return failf(h, PV_ERR_ARGUMENT, "pv_pitch_process: hop %d of channel %d, frame %d is outside [1, fft_size %d]", (int)v, r, m, h->N);
                 t += v;
             }
             if (t > most) most = t;
@@ -227,29 +186,27 @@ int pv_pitch_process(pv_pitch *h, const float *in, float *out, int32_t nch, int3
     int64_t total = 0;
     (void)pv_resample_out_count(h->resample, (int64_t)nframes * h->hs, &total);
     if (nout) *nout = total;
-    if (out_capacity < total) {
-        snprintf(msg, sizeof msg, "pv_pitch_process: out_capacity %lld is below the %lld samples per channel this call produces", (long long)out_capacity,
-                 (long long)total);
-        return pfail(h, PV_ERR_ARGUMENT, msg);
-    }
-    if (!in || (total > 0 && !out)) return pfail(h, PV_ERR_ARGUMENT, "pv_pitch_process: null buffer");
-    if (nch > 1 && (in_stride < most || out_stride < total)) return pfail(h, PV_ERR_ARGUMENT, "pv_pitch_process: channel strides shorter than the input read or the output written");
+    if (out_capacity < total)
+        return failf(h, PV_ERR_ARGUMENT, "pv_pitch_process: out_capacity %lld is below the %lld samples per channel this call produces", (long long)out_capacity,
+                     (long long)total);
+    if (!in || (total > 0 && !out)) return fail(h, PV_ERR_ARGUMENT, "pv_pitch_process: null buffer");
+    if (nch > 1 && (in_stride < most || out_stride < total)) return fail(h, PV_ERR_ARGUMENT, "pv_pitch_process: channel strides shorter than the input read or the output written");
     if (nch == 0 || nframes == 0) return PV_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_process: hipSetDevice failed");
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_process: hipSetDevice failed");
     const size_t dpitch_out = (size_t)(total > 0 ? total : 1);
     int rc = grow(h, &h->d_in, &h->in_cap, (size_t)nch * (size_t)most);
     if (rc == PV_OK) rc = grow(h, &h->d_out, &h->out_cap, (size_t)nch * dpitch_out);
     if (rc != PV_OK) return rc;
     hipError_t e = hipMemcpy2DAsync(h->d_in, sizeof(float) * (size_t)most, in, sizeof(float) * (size_t)(nch > 1 ? in_stride : most), sizeof(float) * (size_t)most,
                                     nch, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_process: copy to the device failed");
+    if (e != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_process: copy to the device failed");
     rc = run(h, "pv_pitch_process", h->d_in, h->d_out, nch, nframes, hops, hop_stride, resets, reset_stride, most, (int64_t)dpitch_out, (int64_t)dpitch_out, nullptr);
     if (rc != PV_OK) return rc;
     if (total > 0)
         e = hipMemcpy2DAsync(out, sizeof(float) * (size_t)(nch > 1 ? out_stride : total), h->d_out, sizeof(float) * dpitch_out, sizeof(float) * (size_t)total, nch,
                              hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return pfail(h, PV_ERR_DEVICE, "pv_pitch_process: copy from the device failed");
+    if (e != hipSuccess) return fail(h, PV_ERR_DEVICE, "pv_pitch_process: copy from the device failed");
     return PV_OK;
 }
 

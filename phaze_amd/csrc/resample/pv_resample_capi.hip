@@ -12,17 +12,15 @@
 
 #include <vector>
 
-#include "../../../include/phaze_amd.h"
+#include "../host/pv_host_common.h"
 #include "pv_resample.h"
 
 namespace {
-constexpr uint32_t kResampleMagic = 0x50565253u;   // 'PVRS'
 constexpr int kMaxTerm = 8192;
 constexpr double kBeta = 9.0, kCutoff = 0.91;
 constexpr int kHalfWidth = 32;
 constexpr long long kPiece = 1LL << 27;            // inputs per launch: outputs (<= 8 x) and every relative index stay inside int32
 constexpr size_t kLdsBudget = 64 * 1024;
-thread_local char g_resample_create_err[256] = "";
 
 struct Ratio { int L, M, W, T; };
 
@@ -102,27 +100,7 @@ struct pv_resample {
 
 namespace {
 
-int rfail(pv_resample *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof h->err, "%s", msg);
-    else snprintf(g_resample_create_err, sizeof g_resample_create_err, "%s", msg);
-    return code;
-}
-
-int rfail_hip(pv_resample *h, hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return rfail(h, PV_ERR_DEVICE, buf);
-}
-
-#define RCHK(h, call)                                              \
-    do {                                                           \
-        hipError_t e_ = (call);                                    \
-        if (e_ != hipSuccess) return rfail_hip((h), e_, #call);    \
-    } while (0)
-
-bool rlive(const pv_resample *h) { return h && h->magic == kResampleMagic; }
+PV_HOST_HANDLE(pv_resample, 0x50565253u /* 'PVRS' */, pv_resample_destroy);
 
 // One piece of at most kPiece inputs over channel slots [0, nch): device pointers, asynchronous on h->stream.  Advances (I, J) and the history.
 int run_piece(pv_resample *h, const float *d_in, float *d_out, int nch, long long nin, long in_stride, long out_stride, long long *produced)
@@ -140,8 +118,8 @@ int run_piece(pv_resample *h, const float *d_in, float *d_out, int nch, long lon
     p.L = r.L; p.M = r.M; p.T = r.T;
     p.nin = (int)nin; p.nout = (int)nout; p.nch = nch;
     p.tile = h->tile; p.lane_stride = h->lane_stride; p.span = h->span;
-    RCHK(h, pv_launch_resample(p, h->shared, h->stream));
-    RCHK(h, pv_launch_resample_history(p, h->stream));
+    HIPCHK(h, pv_launch_resample(p, h->shared, h->stream));
+    HIPCHK(h, pv_launch_resample_history(p, h->stream));
     h->cur ^= 1;
     h->I += nin;
     h->J = J1;
@@ -152,19 +130,14 @@ int run_piece(pv_resample *h, const float *d_in, float *d_out, int nch, long lon
 int check_process(pv_resample *h, const char *fn, const void *in, const void *out, int32_t nch, int64_t nin, int64_t in_stride, int64_t out_stride,
                   int64_t out_capacity, long long *total)
 {
-    char msg[256];
-    if (nch < 0 || nin < 0) { snprintf(msg, sizeof msg, "%s: negative channel or sample count", fn); return rfail(h, PV_ERR_ARGUMENT, msg); }
-    if (nch > h->max_channels) { snprintf(msg, sizeof msg, "%s: more channels than max_channels", fn); return rfail(h, PV_ERR_CAPACITY, msg); }
+    if (nch < 0 || nin < 0) return failf(h, PV_ERR_ARGUMENT, "%s: negative channel or sample count", fn);
+    if (nch > h->max_channels) return failf(h, PV_ERR_CAPACITY, "%s: more channels than max_channels", fn);
     *total = count_of(h->r, h->I + nin) - h->J;
-    if ((nin > 0 && !in) || (*total > 0 && !out)) { snprintf(msg, sizeof msg, "%s: null buffer", fn); return rfail(h, PV_ERR_ARGUMENT, msg); }
-    if (out_capacity < *total) {
-        snprintf(msg, sizeof msg, "%s: out_capacity %lld is below the %lld samples per channel this call produces", fn, (long long)out_capacity, *total);
-        return rfail(h, PV_ERR_ARGUMENT, msg);
-    }
-    if (nch > 1 && (in_stride < nin || out_stride < *total)) {
-        snprintf(msg, sizeof msg, "%s: channel strides shorter than nin (%lld) or the samples produced (%lld)", fn, (long long)nin, *total);
-        return rfail(h, PV_ERR_ARGUMENT, msg);
-    }
+    if ((nin > 0 && !in) || (*total > 0 && !out)) return failf(h, PV_ERR_ARGUMENT, "%s: null buffer", fn);
+    if (out_capacity < *total)
+        return failf(h, PV_ERR_ARGUMENT, "%s: out_capacity %lld is below the %lld samples per channel this call produces", fn, (long long)out_capacity, *total);
+    if (nch > 1 && (in_stride < nin || out_stride < *total))
+        return failf(h, PV_ERR_ARGUMENT, "%s: channel strides shorter than nin (%lld) or the samples produced (%lld)", fn, (long long)nin, *total);
     return PV_OK;
 }
 
@@ -172,7 +145,7 @@ int check_process(pv_resample *h, const char *fn, const void *in, const void *ou
 
 extern "C" {
 
-const char *pv_resample_last_error(const pv_resample *h) { return rlive(h) ? h->err : g_resample_create_err; }
+const char *pv_resample_last_error(const pv_resample *h) { return last_error(h); }
 
 int64_t pv_resample_count(int32_t up, int32_t down, int64_t total_in)
 {
@@ -199,29 +172,25 @@ int64_t pv_resample_design(int32_t up, int32_t down, float *taps, int64_t capaci
 
 int pv_resample_create(const pv_resample_config *cfg, pv_resample **out)
 {
-    if (!cfg || !out) return rfail(nullptr, PV_ERR_ARGUMENT, "pv_resample_create: null argument");
+    if (!cfg || !out) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_resample_create: null argument");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(pv_resample_config))
-        return rfail(nullptr, PV_ERR_ARGUMENT, "pv_resample_create: pv_resample_config.struct_size does not match this library (start from PV_RESAMPLE_CONFIG_INIT)");
-    if (cfg->flags != 0) return rfail(nullptr, PV_ERR_ARGUMENT, "pv_resample_create: unknown bits in pv_resample_config.flags (must be 0)");
+        return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_resample_create: pv_resample_config.struct_size does not match this library (start from PV_RESAMPLE_CONFIG_INIT)");
+    if (cfg->flags != 0) return fail(kNoHandle, PV_ERR_ARGUMENT, "pv_resample_create: unknown bits in pv_resample_config.flags (must be 0)");
     Ratio r;
-    if (const char *why = reduce(cfg->up, cfg->down, &r)) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "pv_resample_create: %s", why);
-        return rfail(nullptr, PV_ERR_ARGUMENT, msg);
-    }
+    if (const char *why = reduce(cfg->up, cfg->down, &r)) return failf(kNoHandle, PV_ERR_ARGUMENT, "pv_resample_create: %s", why);
     const int maxch = cfg->max_channels > 0 ? cfg->max_channels : 1;
     const long long maxs = cfg->max_samples > 0 ? cfg->max_samples : 4096;
-    if (maxch > 65535) return rfail(nullptr, PV_ERR_UNSUPPORTED, "max_channels above 65535 (grid.y limit)");
+    if (maxch > 65535) return fail(kNoHandle, PV_ERR_UNSUPPORTED, "max_channels above 65535 (grid.y limit)");
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return rfail(nullptr, PV_ERR_DEVICE, "no HIP device available (this library has no CPU path)"); }
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return rfail(nullptr, PV_ERR_ARGUMENT, "device_id out of range");
+    if (e != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(kNoHandle, PV_ERR_DEVICE, "no HIP device available (this library has no CPU path)"); }
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(kNoHandle, PV_ERR_ARGUMENT, "device_id out of range");
 
     pv_resample *h = (pv_resample *)calloc(1, sizeof(pv_resample));
-    if (!h) return rfail(nullptr, PV_ERR_DEVICE, "pv_resample_create: out of host memory");
-    h->magic = kResampleMagic;
+    if (!h) return fail(kNoHandle, PV_ERR_DEVICE, "pv_resample_create: out of host memory");
+    h->magic = HostTraits<pv_resample>::kMagic;
     h->r = r;
     h->max_channels = maxch; h->max_samples = maxs; h->device = cfg->device_id;
     h->hist_stride = r.T - 1;
@@ -236,17 +205,8 @@ int pv_resample_create(const pv_resample_config *cfg, pv_resample **out)
     h->tile = PV_RESAMPLE_R * h->lane_stride;
     h->span = (int)(((long long)(h->tile - 1) * r.M + r.L - 1) / r.L) + r.T;
 
-#define CCHK(call)                                                         \
-    do {                                                                   \
-        hipError_t e2_ = (call);                                           \
-        if (e2_ != hipSuccess) {                                           \
-            int rc_ = rfail_hip(nullptr, e2_, #call);                      \
-            pv_resample_destroy(h);                                        \
-            return rc_;                                                    \
-        }                                                                  \
-    } while (0)
-    CCHK(hipSetDevice(h->device));
-    CCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    CREATE_CHK(h, hipSetDevice(h->device));
+    CREATE_CHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
     {
         std::vector<double> rows;
@@ -254,18 +214,17 @@ int pv_resample_create(const pv_resample_config *cfg, pv_resample **out)
         std::vector<float> tr((size_t)r.L * (size_t)r.T);
         for (int ph = 0; ph < r.L; ph++)
             for (int i = 0; i < r.T; i++) tr[(size_t)i * r.L + ph] = (float)rows[(size_t)ph * r.T + i];
-        CCHK(hipMalloc(&h->d_taps, sizeof(float) * tr.size()));
-        CCHK(hipMemcpy(h->d_taps, tr.data(), sizeof(float) * tr.size(), hipMemcpyHostToDevice));
+        CREATE_CHK(h, hipMalloc(&h->d_taps, sizeof(float) * tr.size()));
+        CREATE_CHK(h, hipMemcpy(h->d_taps, tr.data(), sizeof(float) * tr.size(), hipMemcpyHostToDevice));
     }
     const size_t hist = sizeof(float) * (size_t)maxch * (size_t)h->hist_stride;
-    CCHK(hipMalloc(&h->d_hist[0], hist));
-    CCHK(hipMalloc(&h->d_hist[1], hist));
-    CCHK(hipMemset(h->d_hist[0], 0, hist));
-    CCHK(hipMemset(h->d_hist[1], 0, hist));
+    CREATE_CHK(h, hipMalloc(&h->d_hist[0], hist));
+    CREATE_CHK(h, hipMalloc(&h->d_hist[1], hist));
+    CREATE_CHK(h, hipMemset(h->d_hist[0], 0, hist));
+    CREATE_CHK(h, hipMemset(h->d_hist[1], 0, hist));
     h->stage_out_pitch = (maxs * r.L + r.M - 1) / r.M + 1;              // a piece of max_samples inputs never produces more
-    CCHK(hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)maxch * (size_t)maxs));
-    CCHK(hipMalloc(&h->d_stage_out, sizeof(float) * (size_t)maxch * (size_t)h->stage_out_pitch));
-#undef CCHK
+    CREATE_CHK(h, hipMalloc(&h->d_stage_in, sizeof(float) * (size_t)maxch * (size_t)maxs));
+    CREATE_CHK(h, hipMalloc(&h->d_stage_out, sizeof(float) * (size_t)maxch * (size_t)h->stage_out_pitch));
     *out = h;
     return PV_OK;
 }
@@ -273,7 +232,7 @@ int pv_resample_create(const pv_resample_config *cfg, pv_resample **out)
 int pv_resample_destroy(pv_resample *h)
 {
     if (!h) return PV_ERR_ARGUMENT;
-    if (!rlive(h)) return PV_ERR_DESTROYED;
+    if (!live(h)) return PV_ERR_DESTROYED;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     void *ptrs[] = {h->d_taps, h->d_hist[0], h->d_hist[1], h->d_stage_in, h->d_stage_out};
@@ -287,32 +246,32 @@ int pv_resample_destroy(pv_resample *h)
 
 int pv_resample_reset(pv_resample *h)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
-    RCHK(h, hipSetDevice(h->device));
-    RCHK(h, hipMemsetAsync(h->d_hist[h->cur], 0, sizeof(float) * (size_t)h->max_channels * (size_t)h->hist_stride, h->stream));
-    RCHK(h, hipStreamSynchronize(h->stream));
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemsetAsync(h->d_hist[h->cur], 0, sizeof(float) * (size_t)h->max_channels * (size_t)h->hist_stride, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->I = h->J = 0;
     return PV_OK;
 }
 
 int pv_resample_set_stream(pv_resample *h, void *hip_stream)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
-    RCHK(h, hipStreamSynchronize(h->stream));                          // work queued on the old stream is ordered before the new one's
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    HIPCHK(h, hipStreamSynchronize(h->stream));                          // work queued on the old stream is ordered before the new one's
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     return PV_OK;
 }
 
 int pv_resample_synchronize(pv_resample *h)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
-    RCHK(h, hipStreamSynchronize(h->stream));
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return PV_OK;
 }
 
 int pv_resample_out_count(const pv_resample *h, int64_t nin, int64_t *nout)
 {
-    if (!rlive(h) || !nout || nin < 0) return PV_ERR_ARGUMENT;
+    if (!live(h) || !nout || nin < 0) return PV_ERR_ARGUMENT;
     *nout = count_of(h->r, h->I + nin) - h->J;
     return PV_OK;
 }
@@ -320,13 +279,13 @@ int pv_resample_out_count(const pv_resample *h, int64_t nin, int64_t *nout)
 int pv_resample_process_device(pv_resample *h, const float *d_in, int32_t nch, int64_t nin, int64_t in_stride, float *d_out, int64_t out_stride,
                                int64_t out_capacity, int64_t *nout)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
+    if (!live(h)) return PV_ERR_ARGUMENT;
     long long total = 0;
     const int rc = check_process(h, "pv_resample_process_device", d_in, d_out, nch, nin, in_stride, out_stride, out_capacity, &total);
     if (rc != PV_OK) return rc;
     if (nout) *nout = total;
     if (nch == 0 || nin == 0) return PV_OK;
-    RCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     long long done = 0;
     for (long long at = 0; at < nin; at += kPiece) {
         long long got = 0;
@@ -340,27 +299,27 @@ int pv_resample_process_device(pv_resample *h, const float *d_in, int32_t nch, i
 int pv_resample_process(pv_resample *h, const float *in, int32_t nch, int64_t nin, int64_t in_stride, float *out, int64_t out_stride, int64_t out_capacity,
                         int64_t *nout)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
+    if (!live(h)) return PV_ERR_ARGUMENT;
     long long total = 0;
     const int rc = check_process(h, "pv_resample_process", in, out, nch, nin, in_stride, out_stride, out_capacity, &total);
     if (rc != PV_OK) return rc;
     if (nout) *nout = total;
     if (nch == 0 || nin == 0) return PV_OK;
-    RCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     // pieces of at most max_samples inputs through the staging buffers: the state carries across pieces exactly as across calls
     const size_t ipitch = sizeof(float) * (size_t)(nch > 1 ? in_stride : nin), opitch = sizeof(float) * (size_t)(nch > 1 ? out_stride : (total > 0 ? total : 1));
     long long done = 0;
     for (long long at = 0; at < nin; at += h->max_samples) {
         const long long n = nin - at < h->max_samples ? nin - at : h->max_samples;
-        RCHK(h, hipMemcpy2DAsync(h->d_stage_in, sizeof(float) * (size_t)h->max_samples, in + at, ipitch, sizeof(float) * (size_t)n, nch, hipMemcpyHostToDevice,
-                                 h->stream));
+        HIPCHK(h, hipMemcpy2DAsync(h->d_stage_in, sizeof(float) * (size_t)h->max_samples, in + at, ipitch, sizeof(float) * (size_t)n, nch, hipMemcpyHostToDevice,
+                                   h->stream));
         long long got = 0;
         const int r = run_piece(h, h->d_stage_in, h->d_stage_out, nch, n, (long)h->max_samples, (long)h->stage_out_pitch, &got);
         if (r != PV_OK) return r;
         if (got > 0)
-            RCHK(h, hipMemcpy2DAsync(out + done, opitch, h->d_stage_out, sizeof(float) * (size_t)h->stage_out_pitch, sizeof(float) * (size_t)got, nch,
-                                     hipMemcpyDeviceToHost, h->stream));
-        RCHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, hipMemcpy2DAsync(out + done, opitch, h->d_stage_out, sizeof(float) * (size_t)h->stage_out_pitch, sizeof(float) * (size_t)got, nch,
+                                       hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
         done += got;
     }
     return PV_OK;
@@ -368,11 +327,11 @@ int pv_resample_process(pv_resample *h, const float *in, int32_t nch, int64_t ni
 
 int pv_resample_export_state(pv_resample *h, int32_t ch, float *hist, int64_t *total_in, int64_t *total_out)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
-    if (ch < 0 || ch >= h->max_channels) return rfail(h, PV_ERR_CAPACITY, "pv_resample_export_state: channel slot out of range");
-    RCHK(h, hipSetDevice(h->device));
-    RCHK(h, hipStreamSynchronize(h->stream));
-    if (hist) RCHK(h, hipMemcpy(hist, h->d_hist[h->cur] + (size_t)ch * h->hist_stride, sizeof(float) * (size_t)h->hist_stride, hipMemcpyDeviceToHost));
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    if (ch < 0 || ch >= h->max_channels) return fail(h, PV_ERR_CAPACITY, "pv_resample_export_state: channel slot out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hist) HIPCHK(h, hipMemcpy(hist, h->d_hist[h->cur] + (size_t)ch * h->hist_stride, sizeof(float) * (size_t)h->hist_stride, hipMemcpyDeviceToHost));
     if (total_in) *total_in = h->I;
     if (total_out) *total_out = h->J;
     return PV_OK;
@@ -380,13 +339,13 @@ int pv_resample_export_state(pv_resample *h, int32_t ch, float *hist, int64_t *t
 
 int pv_resample_import_state(pv_resample *h, int32_t ch, const float *hist, int64_t total_in, int64_t total_out)
 {
-    if (!rlive(h)) return PV_ERR_ARGUMENT;
-    if (ch < 0 || ch >= h->max_channels) return rfail(h, PV_ERR_CAPACITY, "pv_resample_import_state: channel slot out of range");
+    if (!live(h)) return PV_ERR_ARGUMENT;
+    if (ch < 0 || ch >= h->max_channels) return fail(h, PV_ERR_CAPACITY, "pv_resample_import_state: channel slot out of range");
     if (total_in >= 0 && total_out != count_of(h->r, total_in))
-        return rfail(h, PV_ERR_ARGUMENT, "pv_resample_import_state: total_out is not the output count of total_in (pv_resample_count)");
-    RCHK(h, hipSetDevice(h->device));
-    RCHK(h, hipStreamSynchronize(h->stream));
-    if (hist) RCHK(h, hipMemcpy(h->d_hist[h->cur] + (size_t)ch * h->hist_stride, hist, sizeof(float) * (size_t)h->hist_stride, hipMemcpyHostToDevice));
+        return fail(h, PV_ERR_ARGUMENT, "pv_resample_import_state: total_out is not the output count of total_in (pv_resample_count)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hist) HIPCHK(h, hipMemcpy(h->d_hist[h->cur] + (size_t)ch * h->hist_stride, hist, sizeof(float) * (size_t)h->hist_stride, hipMemcpyHostToDevice));
     if (total_in >= 0) { h->I = total_in; h->J = total_out; }
     return PV_OK;
 }

@@ -424,7 +424,7 @@ int resident_start(pv_handle *h, unsigned last_seq)
     p.fwd64 = h->fwd64 ? 1 : 0; p.fwd_stats = h->d_fwd_stats;
     p.in_cached = h->resident_in_bar ? 1 : 0;
     resident_publish(h, h->h_ctl + 4, 0u);
-    // stale completion words must not match a future 16-bit sequence number (a slot unused for exactly 65535 quanta)
+    // stale completion words must not match a future 16-bit sequence number (see also the wrap in pv_process_begin: a slot unused for 65534 quanta)
     for (int c = 0; c < h->max_channels; c++) h->h_done[c] = 0u;
     const hipError_t e = family_launch_resident(h, p);
     if (e != hipSuccess) return fail_hip(h, e, "resident kernel launch");
@@ -843,7 +843,14 @@ int pv_process_begin(pv_handle *h, const float *const *in, int32_t nch, int32_t 
             h->last_quantum = now;
             if (!h->resident_on) { const int rc = resident_start(h, h->quantum_seq); if (rc != PV_OK) return rc; }
             unsigned seq = (h->quantum_seq + 1u) & 0xFFFFu;                  // the resident protocol carries 16 bits of it (never 0)
-            if (seq == 0) seq = 1;
+            if (seq == 0) {
+                seq = 1;
+                // The numbers start over: no completion word of the cycle before may survive into this one.  A slot that is not part of a quantum stores no
+                // word (PV_FLAG_HOST_CHANNEL_BOOKKEEPING: the channel count may change with the waves staying), so after 65534 quanta without it its word
+                // would equal the next quantum's number and pv_process_end would take the slot for complete before its wave has run.  Nothing is in
+                // flight here (the previous quantum has been collected), and a word written from now on is below every later number of this cycle.
+                for (int c = 0; c < h->max_channels; c++) h->h_done[c] = 0u;
+            }
             h->quantum_seq = seq;
             if (nch > h->used_channels) h->used_channels = nch;
             const unsigned common = seq | ((unsigned)h->cur << 23) | ((unsigned)((h->time_cursor / hop) % h->R) << 24);

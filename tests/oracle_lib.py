@@ -43,6 +43,8 @@ def lib():
         L.pvo_debug_npeaks.argtypes = [C.c_void_p]
         L.pvo_time_cursor.restype = C.c_double
         L.pvo_time_cursor.argtypes = [C.c_void_p]
+        L.pvo_set_time_cursor.restype = None
+        L.pvo_set_time_cursor.argtypes = [C.c_void_p, C.c_double]
         _lib = L
     return _lib
 
@@ -67,6 +69,14 @@ class Oracle:
 
     def __del__(self):
         self.close()
+
+    @property
+    def time_cursor(self) -> float:
+        return lib().pvo_time_cursor(self.h)
+
+    @time_cursor.setter
+    def time_cursor(self, value):
+        lib().pvo_set_time_cursor(self.h, float(value))
 
     def process(self, blocks, pitch: float, paused: bool = False, nout: int = -1):
         """blocks: list of float32[hop] per channel -> list of float32[hop] outputs.  nout: outputs[0].length when it differs from the input channel

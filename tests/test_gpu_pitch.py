@@ -12,10 +12,17 @@ from test_gpu_link import PHASE
 
 pytestmark = pytest.mark.gpu
 
-N, FLOOR, HS, FRAMES = 1024, 205, 320, 61
+FRAMES = 61
+# (N, floor hop, synthesis hop): the resampler runs at up / down = floor / hs.  Which instance of it that is follows pv_resample_create's rule (tests/test_gpu_resample.py)
+SHAPES = [
+    (1024, 205, 320),                # 41/64: the taps-in-LDS instance
+    (1024, 251, 256),                # 251/256: generic, L <= 256 but the table does not fit beside the span
+    (1024, 64, 500),                 # 16/125: generic at decimation, pitch x 7.8
+    (512, 257, 40),                  # 257/40: generic, L above the thread count, pitch x 0.156 (pv_stretch_create accepts the pair: ha <= N, hs <= N / 2, 1/8 <= ha / hs <= 8)
+]
 
 
-def _input(nch, n, seed):
+def _input(N, nch, n, seed):
     rng = np.random.default_rng(seed)
     k = np.arange(n, dtype=np.float64)
     x = np.stack([0.4 * np.cos(2 * np.pi * (60.3 + 11 * c) * k / N + c) + 0.2 * np.cos(2 * np.pi * 171.7 * k / N) + 0.05 * rng.standard_normal(n)
@@ -24,11 +31,12 @@ def _input(nch, n, seed):
     return x.astype(np.float32)
 
 
-def _schedule(kind, rng):
+def _schedule(kind, rng, N, FLOOR, HS):
+    """Hops scale with the shape: from the floor to 400 / 205 of it (at most N), six frames in the middle at unit tempo where the handle allows hop == hs."""
     if kind == "fixed":
         return None, None
-    hops = rng.integers(FLOOR, 400, FRAMES).astype(np.int32)
-    hops[FRAMES // 2:FRAMES // 2 + 6] = HS
+    hops = rng.integers(FLOOR, min(FLOOR * 400 // 205, N + 1), FRAMES).astype(np.int32)
+    hops[FRAMES // 2:FRAMES // 2 + 6] = HS if FLOOR <= HS <= N else FLOOR
     if kind == "hops":
         return hops, None
     resets = np.zeros(FRAMES, np.uint8)
@@ -47,15 +55,16 @@ def _states(stretch, resampler, nch):
 
 @pytest.mark.parametrize("G", [1, 2])
 @pytest.mark.parametrize("kind", ["fixed", "hops", "resets"])
-def test_pitch_handle_is_stretch_then_resample_bit_for_bit(G, kind):
+@pytest.mark.parametrize("N,FLOOR,HS", SHAPES)
+def test_pitch_handle_is_stretch_then_resample_bit_for_bit(N, FLOOR, HS, G, kind):
     import phaze_amd
     import torch
     nch = 2
     rng = np.random.default_rng(17 + G)
-    hops, resets = _schedule(kind, rng)
+    hops, resets = _schedule(kind, rng, N, FLOOR, HS)
     row = np.full(FRAMES, FLOOR, np.int32) if hops is None else hops
     at = np.concatenate([[0], np.cumsum(row.astype(np.int64))])
-    x = _input(nch, int(at[-1]), 5)
+    x = _input(N, nch, int(at[-1]), 5)
     L, M = RM.reduce_ratio(FLOOR, HS)
 
     ts = phaze_amd.TimeStretch(N, FLOOR, HS, max_channels=nch, max_frames=FRAMES, channels_per_group=G)

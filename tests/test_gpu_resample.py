@@ -14,7 +14,19 @@ import test_resample_model as TRM
 
 pytestmark = pytest.mark.gpu
 
-RATIOS = [(4, 5), (5, 4), (2, 3), (3, 2), (1, 2), (2, 1), (1, 8), (8, 1), (100, 97), (97, 100), (147, 160), (160, 147), (8191, 8192), (8192, 8191), (1, 1)]
+# Which instance a ratio takes is pv_resample_create's rule (L <= 256 threads AND the tap table fits beside the tile's span in 64 KB of LDS: the taps-in-LDS
+# instance pv_resample_kernel<true>, else the generic pv_resample_kernel<false>).  No entry point reports it, so it is stated here, worked out from that rule:
+GENERIC_RATIOS = [
+    (16, 125),                       # generic: the smallest L whose table does not fit (decimation 7.8: T = 500 taps, span 8493)
+    (16, 123),                       # shared:  its neighbour on the other side of the LDS budget
+    (100, 227), (100, 223),          # generic, shared: the same boundary at a mid-size L
+    (239, 240),                      # generic: near unity, L <= 256, table too large
+    (232, 233),                      # shared:  the largest such L that still fits
+    (257, 256),                      # generic: the smallest L above the thread count
+    (1024, 8191), (1025, 8192),      # generic at / 8: T = 512, span about 8690, stride-8 LDS reads
+    (8191, 1024), (8192, 1025),      # generic at x 8
+]
+RATIOS = [(4, 5), (5, 4), (2, 3), (3, 2), (1, 2), (2, 1), (1, 8), (8, 1), (100, 97), (97, 100), (147, 160), (160, 147), (8191, 8192), (8192, 8191), (1, 1)] + GENERIC_RATIOS
 NCH = 8
 OUT_TILES = 3 * 1024 + 300                    # a tile holds at most 1024 outputs: more than three per channel
 FP = C.POINTER(C.c_float)
@@ -179,7 +191,7 @@ def test_any_split_of_a_stream_gives_the_same_bits(up, down):
         assert np.array_equal(h1[0], h2[0]) and h1[1:] == h2[1:], what
 
 
-@pytest.mark.parametrize("up,down", [(4, 5), (1, 8), (8, 1), (8191, 8192)])
+@pytest.mark.parametrize("up,down", [(4, 5), (1, 8), (8, 1), (8191, 8192)] + GENERIC_RATIOS)
 def test_a_short_out_capacity_is_refused_with_the_state_untouched(up, down):
     import phaze_amd
     from phaze_amd import capi
@@ -204,6 +216,148 @@ def test_a_short_out_capacity_is_refused_with_the_state_untouched(up, down):
     assert np.array_equal(y, ref)
     rs.reset()
     assert rs.export_state(0)[1:] == (0, 0) and np.array_equal(rs.process(x), ref)        # a reset handle is a fresh one
+
+
+# ---- positions far from zero: (I, J) are int64, every launch derives its (n0, phase0) from them in 128-bit arithmetic (run_piece) ----
+
+FAR_RATIOS = [(4, 5), (1, 8), (8, 1), (147, 160), (1024, 8191), (8191, 1024)]
+FAR_TARGETS = [2 ** 24, 2 ** 31, 2 ** 32, 2 ** 40, 2 ** 62]
+
+
+@pytest.mark.parametrize("up,down", FAR_RATIOS)
+def test_a_stream_position_shifted_by_whole_periods_changes_no_bit(up, down):
+    """For c > W, J(c + k M) = J(c) + k L and output J(c) + k L + j has the phase and the taps of output J(c) + j: a handle that imports A's history at
+    (c + k M, J(c) + k L) must produce A's bits from then on, end with A's history, and count (k M, k L) further.  k: the smallest that puts the LARGER of
+    the two counters just above 2^24, 2^31, 2^32, 2^40 and 2^62 (for L > M the output counter leads; past 2^63 it would leave int64, which is outside the
+    contract).  Host form and device form on a user stream, both in random pieces of their own."""
+    import phaze_amd
+    import torch
+    k_ = case(up, down)
+    nch, L, M, W = 2, k_["L"], k_["M"], k_["W"]
+    c = 2 * W + 7
+    nin = k_["x"].shape[1] + c                                          # the ratio's usual length BEHIND the first c samples: more than three tiles from there
+    x = _signals(nin, up * 7 + down)[:nch]
+    assert RM.count(up, down, nin) - RM.count(up, down, c) > 3 * 1024
+    rng = np.random.default_rng(up * 31 + down)
+    a = phaze_amd.Resampler(up, down, max_channels=nch, max_samples=nin)
+    a.process(x[:, :c])
+    start = [a.export_state(ch) for ch in range(nch)]
+    Jc = start[0][2]
+    assert (start[0][1], Jc) == (c, RM.count(up, down, c))
+    ya = _feed_from(a, x[:, c:], _sizes(nin - c, lambda: int(rng.integers(1, 3000))))
+    hist_a, Ia, Ja = _state(a, nch)
+    stream = torch.cuda.Stream()
+    d_in = torch.from_numpy(x[:, c:].copy()).cuda()
+    for target in FAR_TARGETS:
+        k = target // max(L, M) + 1
+        assert max(k * L, k * M) > target and k * max(L, M) + 8 * nin < 2 ** 63
+        for form in ("host", "device"):
+            b = phaze_amd.Resampler(up, down, max_channels=nch, max_samples=4096)
+            for ch in range(nch):
+                b.import_state(ch, start[ch][0], c + k * M, Jc + k * L)
+            sizes = _sizes(nin - c, lambda: int(rng.integers(1, 4000)))
+            if form == "host":
+                yb = _feed_from(b, x[:, c:], sizes)
+            else:
+                b.set_stream(stream.cuda_stream)
+                d_out = torch.full((nch, ya.shape[1] + 5), -77.0, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                at = done = 0
+                for n in sizes:
+                    got = b.process_device(d_in.data_ptr() + 4 * at, nch, n, nin - c, d_out.data_ptr() + 4 * done, ya.shape[1] + 5, ya.shape[1] - done)
+                    at, done = at + n, done + got
+                b.synchronize()
+                yd = d_out.cpu().numpy()
+                assert done == ya.shape[1] and np.all(yd[:, done:] == -77.0)
+                yb = np.ascontiguousarray(yd[:, :done])
+                b.set_stream(None)
+            what = f"{form} form, k M = {k * M}, k L = {k * L}"
+            assert yb.shape == ya.shape and np.array_equal(yb.view(np.uint32), ya.view(np.uint32)), what
+            hist_b, Ib, Jb = _state(b, nch)
+            assert np.array_equal(hist_b.view(np.uint32), hist_a.view(np.uint32)) and (Ib, Jb) == (Ia + k * M, Ja + k * L), what
+            b.close()
+    a.close()
+
+
+def _feed_from(rs, x, sizes):
+    """Feed x in host calls of the given sizes from wherever the handle stands, checking every count against the handle's own closed form."""
+    at, parts = 0, []
+    I0 = rs.export_state(0)[1]
+    for n in sizes:
+        want = RM.count(rs.up, rs.down, I0 + at + n) - RM.count(rs.up, rs.down, I0 + at)
+        assert rs.out_count(n) == want
+        parts.append(rs.process(x[:, at:at + n]))
+        assert parts[-1].shape[1] == want
+        at += n
+    assert at == x.shape[1]
+    return np.concatenate(parts, axis=1)
+
+
+@pytest.mark.parametrize("up,down", [(4, 5), (100, 97), (16, 125), (8191, 8192)])
+def test_a_stream_picked_up_at_2_to_the_40_is_within_the_derived_bound_of_the_model(up, down):
+    """A position that is no multiple of anything: I0 = 2^40 + 12345, J0 = J(I0), a random history.  The model's index arithmetic is Python / int64 and holds
+    there (tests/test_resample_model.py checks it against a shifted run); the bound is the file's own, no sample left out."""
+    import phaze_amd
+    k = case(up, down)
+    nch, x = 2, k["x"][:2]
+    I0 = 2 ** 40 + 12345
+    J0 = RM.count(up, down, I0)
+    assert phaze_amd.resample_count(up, down, I0) == J0
+    hist = (np.random.default_rng(up + down).standard_normal((nch, k["T"] - 1)) * 0.5).astype(np.float32)
+    m = RM.ResampleModel(up, down, nch, k["taps"])
+    m.hist[:], m.I, m.J = hist, I0, J0
+    ym, bm = m.process(x, bound=True)
+    assert ym.shape[1] == RM.count(up, down, I0 + x.shape[1]) - J0 >= 3 * 1024
+    rs = phaze_amd.Resampler(up, down, max_channels=nch, max_samples=x.shape[1])
+    for ch in range(nch):
+        rs.import_state(ch, hist[ch], I0, J0)
+    y = rs.process(x)
+    tol = (k["T"] + 1) * 2.0 ** -24 * bm
+    err = np.abs(y.astype(np.float64) - ym)
+    worst = float(np.max(err / np.maximum(tol, 1e-300)))
+    print(f"{up}/{down} from 2^40 + 12345: worst |err| / bound = {worst:.3f}, max |err| = {err.max():.3e}")
+    assert y.shape == ym.shape and np.all(err <= tol), (int(np.sum(err > tol)), worst)
+    h2, I2, J2 = _state(rs, nch)
+    assert np.array_equal(h2, m.hist) and (I2, J2) == (m.I, m.J) == (I0 + x.shape[1], J0 + y.shape[1])
+    rs.close()
+
+
+def test_one_device_call_longer_than_a_launch_piece_equals_two_calls():
+    """The only test here that is large by necessity: pv_resample_process_device cuts a call into launches of at most 2^27 inputs (kPiece), and only a call
+    longer than that runs the loop.  One channel at 1/8, 2^27 + 5000 samples made on the device (0.54 GB in, 67 MB out): one call of the whole against two
+    calls split at 2^26 + 333 on a second handle.  Same samples, same counters; nothing but the counters and three booleans leaves the device.
+    Measured on an MI355X: 1.4 ms of device work per handle, 0.19 s for the test.  The same at 8/1 would write 4.3 GB per handle on a card the suite
+    shares; it is left out -- at 8/1 the launch differs from this one in its output count only, and that stays below 2^31 by kPiece's choice."""
+    import time
+
+    import phaze_amd
+    import torch
+    up, down, nin, cut = 1, 8, 2 ** 27 + 5000, 2 ** 26 + 333
+    nout = RM.count(up, down, nin)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(5)
+    d_in = torch.randn(nin, dtype=torch.float32, device="cuda", generator=gen)
+    outs, counters = [], []
+    for calls in ([nin], [cut, nin - cut]):
+        rs = phaze_amd.Resampler(up, down, max_channels=1, max_samples=4096)
+        d_out = torch.full((nout + 16,), -77.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        at = done = 0
+        for n in calls:
+            done += rs.process_device(d_in.data_ptr() + 4 * at, 1, n, nin, d_out.data_ptr() + 4 * done, nout + 16, nout - done)
+            at += n
+        rs.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"1/8 over {nin} samples in {len(calls)} call(s): {dt * 1e3:.1f} ms")
+        assert done == nout and bool(torch.all(d_out[nout:] == -77.0))
+        outs.append(d_out)
+        i, j = C.c_int64(), C.c_int64()
+        assert rs._L.pv_resample_export_state(rs._h, 0, None, C.byref(i), C.byref(j)) == 0          # the counters alone: no sample leaves the device
+        counters.append((i.value, j.value))
+        rs.close()
+    assert counters[0] == counters[1] == (nin, nout)
+    assert torch.equal(outs[0], outs[1]) and bool(torch.isfinite(outs[0]).all()) and float(outs[0][:nout].abs().max()) > 0.1
 
 
 def _f32_bound(taps):

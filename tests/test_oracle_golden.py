@@ -104,3 +104,22 @@ def test_known_answer_stereo_equals_two_monos():
     for c in range(2):
         ym = oracle_lib.Oracle(N, h, 1).process_planar(xs[c:c + 1], p)
         assert np.array_equal(ys[c], ym[0])
+
+
+@pytest.mark.parametrize("k", [7, 1000])
+def test_setting_the_time_cursor_equals_consuming_silence(k):
+    """pvo_set_time_cursor(k * hop) puts a fresh oracle where k hops of silence put it (silence leaves every buffer zero, only timeCursor moves, pv:71):
+    the outputs that follow are the same bits.  tests/test_gpu_long_streams.py starts the oracle far out this way."""
+    N, h, T = 1024, 256, 12
+    x = np.stack([S.make_signal("tonal", c, T * h) for c in range(2)])
+    p = np.linspace(0.7, 1.6, T).astype(np.float32)
+    a = oracle_lib.Oracle(N, h, 2)
+    a.process_planar(np.zeros((2, k * h), np.float32), np.ones(k, np.float32))
+    assert a.time_cursor == k * h
+    b = oracle_lib.Oracle(N, h, 2)
+    b.process_planar(np.zeros((2, h), np.float32), np.ones(1, np.float32))      # the channel buffers exist (ola:38-52) before the cursor is set
+    b.time_cursor = k * h
+    assert b.time_cursor == k * h
+    ya, yb = a.process_planar(x, p), b.process_planar(x, p)
+    assert np.array_equal(ya.view(np.uint32), yb.view(np.uint32)) and np.any(ya != 0)
+    assert a.time_cursor == b.time_cursor == (k + T) * h

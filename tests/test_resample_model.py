@@ -116,6 +116,29 @@ def test_any_split_of_a_stream_gives_the_same_model_output(up, down):
         assert np.array_equal(m.hist, whole.hist) and (m.I, m.J) == (whole.I, whole.J)
 
 
+@pytest.mark.parametrize("up,down", [(4, 5), (100, 97), (16, 125), (8191, 8192)])
+def test_a_model_set_to_a_position_continues_like_one_that_got_there(up, down):
+    """tests/test_gpu_resample.py starts the model at 2^40 + 12345 by assigning hist, I and J.  That is sound if (a) a model set to a small position it could
+    have reached continues exactly like the one that did reach it, and (b) the index arithmetic holds far out: shifted by k M inputs / k L outputs the phases
+    repeat, so the outputs must be the same doubles -- at k M just above 2^40 and as far out as the model's own int64 product j M allows (j M ~ 2^62)."""
+    rng = np.random.default_rng(up + 3 * down)
+    one = RM.ResampleModel(up, down, 2)
+    I0 = 3 * one.T + 12345 % one.T
+    nin = I0 + 6 * one.T + 50 * max(1, down // up)
+    x = rng.standard_normal((2, nin)).astype(np.float32)
+    one.process(x[:, :I0])
+    hist = one.hist.copy()
+    want = one.process(x[:, I0:])
+    assert want.shape[1] > 0
+    for k in (0, 2 ** 40 // one.M + 1, 2 ** 62 // (one.L * one.M)):
+        m = RM.ResampleModel(up, down, 2)
+        m.hist[:], m.I, m.J = hist, I0 + k * m.M, RM.count(up, down, I0) + k * m.L
+        assert m.J == RM.count(up, down, m.I)
+        got = m.process(x[:, I0:])
+        assert got.shape == want.shape and np.array_equal(got, want), k
+        assert np.array_equal(m.hist, one.hist) and (m.I, m.J) == (one.I + k * m.M, one.J + k * m.L)
+
+
 # ---- the composition: StretchModel followed by the resampler at ha / hs, against the closed form --------------------------------------------
 
 def envelope_at(N, hs, t):

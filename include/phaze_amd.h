@@ -52,7 +52,8 @@ typedef struct pv_handle pv_handle;
  * 6 = the time-stretch handle (pv_stretch_config, pv_stretch_*); nothing that existed changed.  Later, still 6 (additive: new symbols only, no
  *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device; linked channels,
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
- *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*. */
+ *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
+ *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -477,6 +478,109 @@ PV_API int pv_pitch_process_device(pv_pitch *h, const float *d_in, float *d_out,
  * destroy them, give them another stream, or process through them directly. */
 PV_API pv_stretch *pv_pitch_stretch(pv_pitch *h);
 PV_API pv_resample *pv_pitch_resampler(pv_pitch *h);
+
+/* ---- variable-ratio band-limited resampling (a separate handle) ------------------------------------------------------------------------ */
+/* The stream moves in blocks of B = block input samples; block b emits counts[b] output samples, min_count <= counts[b] <= max_count, so the local
+ * step B / counts[b] (input samples per output sample: the pitch factor) changes from block to block.  1 <= B <= 4096, 1 <= min_count <= max_count
+ * <= 8192, B <= 8 min_count and max_count <= 8 B (the step stays within [1/8, 8]); anything else PV_ERR_ARGUMENT.  Half width W = ceil(32 max(1, B /
+ * min_count)) <= 256 input samples, T = 2 W.  Output k of stream block b with count c sits at input position b B + k B / c - W: with n = b B + (k B) div c
+ * and r = (k B) mod c, tap i = 0 .. T - 1 reads x[n - 2 W + 1 + i] (x zero before the stream) at distance a = |(i - W + 1) c - r| / c from it.  One
+ * prototype serves every ratio: P[q] = f32(h0(q / 256)), h0(t) = 0.91 sinc(0.91 t) I0(9 sqrt(1 - (t / 32)^2)) / I0(9), P = 0 from q = 32 * 256 on
+ * (pv_vari_prototype).  With den = max(B, c) (the filter widens by max(1, B / c) where a block decimates), in exact integers q = (256 a) div den and
+ * rem = (256 a) mod den; the weight is w_i = P[q] + (rem / den) (P[q + 1] - P[q]), 0 when q >= 32 * 256, and
+ *     y = (sum_i w_i x_i) / (sum_i w_i),
+ * both sums in f32 with i ascending (one fused multiply-add and one add per tap), then one f32 division: unit DC gain at every position and ratio,
+ * and the same bits whatever the tiling.  The output lags by W input samples; every output of a block is computable once the block is in, so a call
+ * of nblocks blocks consumes nblocks * B samples per channel and writes sum(counts).  The carried state is the newest T - 1 input samples per slot;
+ * the int64 counters (blocks, outputs) are informational.  All channel slots of a handle move together.  See INTEGRATION.md "Pitch curves". */
+typedef struct pv_vari_config {
+    int32_t struct_size;     /* sizeof(pv_vari_config) as the caller compiled it (PV_VARI_CONFIG_INIT sets it)                   */
+    int32_t block;           /* B, input samples per block                                                                       */
+    int32_t min_count;       /* the smallest count a call may pass                                                               */
+    int32_t max_count;       /* the largest                                                                                      */
+    int32_t max_channels;    /* channel slots (0 => 1)                                                                           */
+    int32_t max_blocks;      /* host-pointer calls: staging size in blocks (0 => about 4096 samples); longer calls go in pieces  */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_vari_config;
+#define PV_VARI_CONFIG_INIT { (int32_t)sizeof(pv_vari_config), 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_vari pv_vari;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_vari_last_error(NULL). */
+PV_API int pv_vari_create(const pv_vari_config *cfg, pv_vari **out);
+PV_API int pv_vari_destroy(pv_vari *h);
+/* Zero every slot's history and the counters: a freshly created handle. */
+PV_API int pv_vari_reset(pv_vari *h);
+PV_API const char *pv_vari_last_error(const pv_vari *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_vari_set_stream(pv_vari *h, void *hip_stream);
+PV_API int pv_vari_synchronize(pv_vari *h);
+/* nblocks blocks for channel slots 0 .. nch-1: read in[c*in_stride .. + nblocks*B), write *nout = sum(counts) samples per channel to
+ * out[c*out_stride ..) (nout may be NULL; it is written before the call returns).  `counts` is a HOST array in both forms, read before the call
+ * returns.  Rejected with PV_ERR_ARGUMENT before any device work, with the state untouched: a null buffer or null counts, negative numbers, a count
+ * outside [min_count, max_count] (the message names the block), out_capacity below sum(counts) and, with nch > 1, strides below nblocks*B / sum(counts).
+ * nch > max_channels: PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of max_blocks. */
+PV_API int pv_vari_process(pv_vari *h, const float *in, int32_t nch, int64_t nblocks, const int32_t *counts, int64_t in_stride, float *out,
+                           int64_t out_stride, int64_t out_capacity, int64_t *nout);
+/* The same on DEVICE in / out pointers, asynchronous on the handle's stream. */
+PV_API int pv_vari_process_device(pv_vari *h, const float *d_in, int32_t nch, int64_t nblocks, const int32_t *counts, int64_t in_stride, float *d_out,
+                                  int64_t out_stride, int64_t out_capacity, int64_t *nout);
+/* State of ONE channel slot, hist[T - 1] = its newest input samples (oldest first), and the handle's counters (blocks consumed, outputs produced).  A
+ * handle that imports what another exported continues bit for bit.  Synchronous; any pointer may be NULL (skipped); pv_vari_import_state leaves the
+ * counters when total_blocks is negative. */
+PV_API int pv_vari_export_state(pv_vari *h, int32_t ch, float *hist, int64_t *total_blocks, int64_t *total_out);
+PV_API int pv_vari_import_state(pv_vari *h, int32_t ch, const float *hist, int64_t total_blocks, int64_t total_out);
+/* Pure host code, no handle and no device.  pv_vari_prototype: the table P the kernel uses, 32 * 256 + 2 = 8194 floats with its guard entries, with
+ * the two-call sizing of pv_transient_plan (returns 8194, writes at most `capacity`).  pv_vari_half_width: W of a config, or -PV_ERR_ARGUMENT with the
+ * reason in pv_vari_last_error(NULL). */
+PV_API int64_t pv_vari_prototype(float *table, int64_t capacity);
+PV_API int32_t pv_vari_half_width(int32_t block, int32_t min_count, int32_t max_count);
+
+/* ---- pitch curves through the stretch: a time-stretch handle followed by a variable-ratio resampler ------------------------------------- */
+/* Frame m consumes hops[m] input samples; the stretch emits synthesis_hop samples for it at constant pitch and the resampler turns that block back
+ * into hops[m] samples: duration is kept sample for sample and frame m is shifted in pitch by synthesis_hop / hops[m], with the stretch's phase
+ * locking, linked channels and phase resets.  The handle owns one pv_stretch (analysis_hop = min_hop, the floor of every schedule) and one pv_vari
+ * (block = synthesis_hop, counts within [min_hop, max_hop]) and drives them through pv_transient_process_device and pv_vari_process_device on one
+ * stream; the stretched signal stays in device memory.  min_hop <= hops[m] <= max_hop <= fft_size, synthesis_hop <= 8 min_hop and max_hop <= 8
+ * synthesis_hop.  The content lags by (fft_size - synthesis_hop) + W samples of the stretched signal, and the curve acts at output time: a caller
+ * shifts the curve by that lag.  tempo_hops(1 / pitch, ...) of the bindings turns a pitch curve into the hop row.  Replaces the pitch fader of the
+ * reference's application (/root/reference/src/main.js:75-96). */
+typedef struct pv_glide_config {
+    int32_t struct_size;     /* sizeof(pv_glide_config) as the caller compiled it (PV_GLIDE_CONFIG_INIT sets it)                  */
+    int32_t fft_size;        /* as pv_stretch_config                                                                             */
+    int32_t synthesis_hop;   /* hs: the stretch's output per frame, the resampler's block                                        */
+    int32_t min_hop;         /* the smallest hop a call may pass (highest pitch: hs / min_hop)                                   */
+    int32_t max_hop;         /* the largest (lowest pitch: hs / max_hop)                                                         */
+    int32_t max_channels;    /* channel slots (0 => 1)                                                                           */
+    int32_t max_frames;      /* frames per call the device buffers are sized for at creation (0 => 1); they grow on demand       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_glide_config;
+#define PV_GLIDE_CONFIG_INIT { (int32_t)sizeof(pv_glide_config), 0, 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_glide pv_glide;
+
+/* Config errors (the stretch's, the resampler's, and max_hop > fft_size) are returned before any device is touched; pv_glide_last_error(NULL). */
+PV_API int pv_glide_create(const pv_glide_config *cfg, pv_glide **out);
+PV_API int pv_glide_destroy(pv_glide *h);
+PV_API int pv_glide_reset(pv_glide *h);
+PV_API const char *pv_glide_last_error(const pv_glide *h);
+/* Both inner handles follow: they always share one stream. */
+PV_API int pv_glide_set_stream(pv_glide *h, void *hip_stream);
+PV_API int pv_glide_synchronize(pv_glide *h);
+/* nframes frames on ONE HOST row of hops for all channels (required when nframes > 0): channel c reads in[c*in_stride .. + sum(hops)) and writes
+ * out[c*out_stride .. + sum(hops)).  resets: as pv_transient_process (NULL: none).  Everything pv_transient_process rejects is rejected here, and a hop
+ * outside [min_hop, max_hop], with PV_ERR_ARGUMENT before any device work and both states untouched.  Host pointers, synchronous. */
+PV_API int pv_glide_process(pv_glide *h, const float *in, float *out, int32_t nch, int32_t nframes, const int32_t *hops, const uint8_t *resets,
+                            int64_t reset_stride, int64_t in_stride, int64_t out_stride);
+/* The same on DEVICE in / out pointers, asynchronous on the handle's stream. */
+PV_API int pv_glide_process_device(pv_glide *h, const float *d_in, float *d_out, int32_t nch, int32_t nframes, const int32_t *hops,
+                                   const uint8_t *resets, int64_t reset_stride, int64_t in_stride, int64_t out_stride);
+/* The inner handles (owned by h, NULL for a dead handle): pv_link_channels and state export / import work through them.  Do not destroy them, give
+ * them another stream, or process through them directly. */
+PV_API pv_stretch *pv_glide_stretch(pv_glide *h);
+PV_API pv_vari *pv_glide_resampler(pv_glide *h);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,10 @@ EXPORTS = [
     "pv_resample_design", "pv_resample_count",
     "pv_pitch_create", "pv_pitch_destroy", "pv_pitch_reset", "pv_pitch_last_error", "pv_pitch_set_stream", "pv_pitch_synchronize",
     "pv_pitch_process", "pv_pitch_process_device", "pv_pitch_stretch", "pv_pitch_resampler",
+    "pv_vari_create", "pv_vari_destroy", "pv_vari_reset", "pv_vari_last_error", "pv_vari_set_stream", "pv_vari_synchronize",
+    "pv_vari_process", "pv_vari_process_device", "pv_vari_export_state", "pv_vari_import_state", "pv_vari_prototype", "pv_vari_half_width",
+    "pv_glide_create", "pv_glide_destroy", "pv_glide_reset", "pv_glide_last_error", "pv_glide_set_stream", "pv_glide_synchronize",
+    "pv_glide_process", "pv_glide_process_device", "pv_glide_stretch", "pv_glide_resampler",
 ]
 
 
@@ -58,6 +62,24 @@ class _ResampleConfig(C.Structure):
 class _PitchConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "fft_size", "analysis_hop", "synthesis_hop", "up", "down", "max_channels", "max_frames", "device_id",
                                           "flags")]
+
+
+class _VariConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "block", "min_count", "max_count", "max_channels", "max_blocks", "device_id", "flags")]
+
+
+class _GlideConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "fft_size", "synthesis_hop", "min_hop", "max_hop", "max_channels", "max_frames", "device_id", "flags")]
+
+
+def make_vari_config(block, min_count, max_count, max_channels=1, max_blocks=0, device_id=0, flags=0):
+    """pv_vari_config with struct_size filled in (the C side's PV_VARI_CONFIG_INIT)."""
+    return _VariConfig(C.sizeof(_VariConfig), block, min_count, max_count, max_channels, max_blocks, device_id, flags)
+
+
+def make_glide_config(fft_size, synthesis_hop, min_hop, max_hop, max_channels=1, max_frames=1, device_id=0, flags=0):
+    """pv_glide_config with struct_size filled in (the C side's PV_GLIDE_CONFIG_INIT)."""
+    return _GlideConfig(C.sizeof(_GlideConfig), fft_size, synthesis_hop, min_hop, max_hop, max_channels, max_frames, device_id, flags)
 
 
 def make_resample_config(up, down, max_channels=1, max_samples=0, device_id=0, flags=0):
@@ -198,6 +220,28 @@ def load_library():
     L.pv_pitch_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, C.c_int64, bp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, lp]
     L.pv_pitch_stretch.argtypes = [vp]
     L.pv_pitch_resampler.argtypes = [vp]
+    L.pv_vari_create.argtypes = [C.POINTER(_VariConfig), C.POINTER(vp)]
+    L.pv_vari_destroy.argtypes = [vp]
+    L.pv_vari_reset.argtypes = [vp]
+    L.pv_vari_last_error.argtypes = [vp]
+    L.pv_vari_set_stream.argtypes = [vp, vp]
+    L.pv_vari_synchronize.argtypes = [vp]
+    L.pv_vari_process.argtypes = [vp, fp, C.c_int32, C.c_int64, ip, C.c_int64, fp, C.c_int64, C.c_int64, lp]
+    L.pv_vari_process_device.argtypes = [vp, vp, C.c_int32, C.c_int64, ip, C.c_int64, vp, C.c_int64, C.c_int64, lp]
+    L.pv_vari_export_state.argtypes = [vp, C.c_int32, fp, lp, lp]
+    L.pv_vari_import_state.argtypes = [vp, C.c_int32, fp, C.c_int64, C.c_int64]
+    L.pv_vari_prototype.argtypes = [fp, C.c_int64]
+    L.pv_vari_half_width.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.pv_glide_create.argtypes = [C.POINTER(_GlideConfig), C.POINTER(vp)]
+    L.pv_glide_destroy.argtypes = [vp]
+    L.pv_glide_reset.argtypes = [vp]
+    L.pv_glide_last_error.argtypes = [vp]
+    L.pv_glide_set_stream.argtypes = [vp, vp]
+    L.pv_glide_synchronize.argtypes = [vp]
+    L.pv_glide_process.argtypes = [vp, fp, fp, C.c_int32, C.c_int32, ip, bp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_glide_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, bp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_glide_stretch.argtypes = [vp]
+    L.pv_glide_resampler.argtypes = [vp]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -205,6 +249,10 @@ def load_library():
     L.pv_resample_design.restype = L.pv_resample_count.restype = C.c_int64
     L.pv_resample_last_error.restype = L.pv_pitch_last_error.restype = C.c_char_p
     L.pv_pitch_stretch.restype = L.pv_pitch_resampler.restype = vp
+    L.pv_vari_prototype.restype = C.c_int64
+    L.pv_vari_half_width.restype = C.c_int32
+    L.pv_vari_last_error.restype = L.pv_glide_last_error.restype = C.c_char_p
+    L.pv_glide_stretch.restype = L.pv_glide_resampler.restype = vp
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -255,7 +303,7 @@ def pinned_empty(shape, dtype=np.float32):
 
 
 class _Handle:
-    """What the four handle classes share: create-and-raise, close, the status check and reset / set_stream / synchronize.  `_prefix` is the C
+    """What the handle classes share: create-and-raise, close, the status check and reset / set_stream / synchronize.  `_prefix` is the C
     prefix of the handle type's entry points (<prefix>_create, _destroy, _last_error, _reset, _set_stream, _synchronize)."""
 
     _prefix = None
@@ -939,3 +987,155 @@ class PitchStretch(_Handle):
         self._check(self._L.pv_pitch_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, nframes, hp, stride, rp, rstride, in_stride, out_stride,
                                                     out_capacity, C.byref(got)))
         return got.value
+
+
+def vari_prototype():
+    """pv_vari_prototype: the table P float32[8194] the variable-ratio kernel interpolates its weights from (P[q] = h0(q / 256), 0 from q = 8192 on)."""
+    L_ = load_library()
+    n = L_.pv_vari_prototype(None, 0)
+    table = np.zeros(n, np.float32)
+    L_.pv_vari_prototype(_fp(table), n)
+    return table
+
+
+def vari_half_width(block, min_count, max_count):
+    """pv_vari_half_width: W = ceil(32 max(1, block / min_count)) of a VariResampler config; ValueError for a config pv_vari_create refuses."""
+    L_ = load_library()
+    w = L_.pv_vari_half_width(int(block), int(min_count), int(max_count))
+    if w < 0:
+        raise ValueError(L_.pv_vari_last_error(None).decode())
+    return int(w)
+
+
+class VariResampler(_Handle):
+    """Variable-ratio band-limited resampler (pv_vari_*): block b of `block` input samples emits counts[b] output samples, min_count <= counts[b] <=
+    max_count, so the step block / counts[b] (the pitch factor) changes from block to block.  The output lags by `latency` input samples.  State
+    carries across calls: any split of a stream into calls gives the same bits."""
+
+    _prefix = "pv_vari"
+    _fft_size_is_value_error = False
+
+    def __init__(self, block, min_count, max_count, max_channels=1, max_blocks=0, device_id=0, _borrowed=None):
+        self._owned = _borrowed is None
+        if _borrowed is not None:
+            self._bind(_borrowed)
+        else:
+            self._create(make_vari_config(block, min_count, max_count, max_channels, max_blocks, device_id, 0))
+        self.block, self.min_count, self.max_count, self.max_channels = block, min_count, max_count, max_channels
+        self.half_width = vari_half_width(block, min_count, max_count)
+        self.taps = 2 * self.half_width
+
+    @property
+    def latency(self):
+        """The output's lag in input samples (the half width W)."""
+        return self.half_width
+
+    @staticmethod
+    def _counts(counts):
+        c = np.ascontiguousarray(counts, dtype=np.int32)
+        if c.ndim != 1:
+            raise ValueError("counts must be int[nblocks]")
+        return c
+
+    def process(self, x, counts):
+        """x: float32[nch, nblocks * block] (host), counts: int[nblocks] -> float32[nch, counts.sum()] for channel slots 0 .. nch-1."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        c = self._counts(counts)
+        nch, nin = x.shape
+        if nin != c.size * self.block:
+            raise ValueError(f"the input holds {nin} samples per channel, {c.size} blocks of {self.block} consume {c.size * self.block}")
+        cap = int(c.astype(np.int64).sum())
+        y = np.empty((nch, cap), np.float32)
+        n = C.c_int64()
+        self._check(self._L.pv_vari_process(self._h, _fp(x), nch, c.size, c.ctypes.data_as(C.POINTER(C.c_int32)), nin, _fp(y), cap, cap, C.byref(n)))
+        assert n.value == cap
+        return y
+
+    def process_device(self, d_in, nch, counts, in_stride, d_out, out_stride, out_capacity):
+        """Raw device pointers (ints), counts a host row.  Asynchronous on the handle's stream; returns the samples written per channel."""
+        c = self._counts(counts)
+        n = C.c_int64()
+        self._check(self._L.pv_vari_process_device(self._h, C.c_void_p(d_in), nch, c.size, c.ctypes.data_as(C.POINTER(C.c_int32)), in_stride, C.c_void_p(d_out),
+                                                   out_stride, out_capacity, C.byref(n)))
+        return n.value
+
+    def export_state(self, ch):
+        """(hist float32[T - 1], blocks, outputs) of channel slot `ch`."""
+        hist = np.zeros(self.taps - 1, np.float32)
+        i, j = C.c_int64(), C.c_int64()
+        self._check(self._L.pv_vari_export_state(self._h, ch, _fp(hist), C.byref(i), C.byref(j)))
+        return hist, i.value, j.value
+
+    def import_state(self, ch, hist=None, blocks=-1, outputs=0):
+        if hist is not None:
+            hist = np.ascontiguousarray(hist, dtype=np.float32)
+            if hist.size != self.taps - 1:
+                raise ValueError(f"state array of {hist.size} values, {self.taps - 1} expected")
+        self._check(self._L.pv_vari_import_state(self._h, ch, _fp(hist) if hist is not None else None, int(blocks), int(outputs)))
+
+
+class PitchGlide(_Handle):
+    """Pitch curves through the time stretch (pv_glide_*): frame m consumes hops[m] input samples and emits hops[m] output samples, shifted in pitch
+    by synthesis_hop / hops[m]; min_hop <= hops[m] <= max_hop.  Duration is kept sample for sample.  tempo_hops(1 / pitch, synthesis_hop, min_hop,
+    max_hop) turns a per-frame pitch curve into the hop row; the curve acts at output time, `latency` stretched samples behind the content.
+    `.stretch` and `.resampler` are the inner handles."""
+
+    _prefix = "pv_glide"
+
+    def __init__(self, fft_size, synthesis_hop, min_hop, max_hop, max_channels=1, max_frames=1, channels_per_group=1, device_id=0):
+        self._create(make_glide_config(fft_size, synthesis_hop, min_hop, max_hop, max_channels, max_frames, device_id, 0))
+        self.fft_size, self.synthesis_hop, self.min_hop, self.max_hop = fft_size, synthesis_hop, min_hop, max_hop
+        self.max_channels = max_channels
+        self.stretch = _BorrowedStretch(self._L.pv_glide_stretch(self._h), fft_size, min_hop, synthesis_hop, max_channels)
+        self.resampler = VariResampler(synthesis_hop, min_hop, max_hop, max_channels, _borrowed=self._L.pv_glide_resampler(self._h))
+        if channels_per_group != 1:
+            try:
+                self.stretch.link_channels(channels_per_group)
+            except Exception:
+                self.close()
+                raise
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.stretch.close()
+            self.resampler.close()
+        super().close()
+
+    @property
+    def latency(self):
+        """The content's lag in samples of the stretched signal: (N - hs) + W."""
+        return (self.fft_size - self.synthesis_hop) + self.resampler.half_width
+
+    def _rows(self, hops, resets):
+        h = np.ascontiguousarray(hops, dtype=np.int32)
+        if h.ndim != 1:
+            raise ValueError("hops must be int[nframes]: one row for all channels")
+        r, rstride = None, 0
+        if resets is not None:
+            r, rstride = TimeStretch._reset_rows(resets, h.size)
+        return h, r, rstride
+
+    def process(self, x, hops, resets=None):
+        """x: float32[nch, hops.sum()] (host), hops: int[nframes], resets: 0 / 1 per frame as TimeStretch.process_hops -> float32 of the shape of x."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        h, r, rstride = self._rows(hops, resets)
+        rp = r.ctypes.data_as(C.POINTER(C.c_uint8)) if r is not None else None
+        if int(h.astype(np.int64).sum()) != n:
+            raise ValueError(f"the input holds {n} samples per channel, the schedule consumes {int(h.astype(np.int64).sum())}")
+        y = np.empty((nch, n), np.float32)
+        if nch and h.size:
+            self._check(self._L.pv_glide_process(self._h, _fp(x), _fp(y), nch, h.size, h.ctypes.data_as(C.POINTER(C.c_int32)), rp, rstride, n, n))
+        return y[0] if one else y
+
+    def process_device(self, d_in, d_out, nch, hops, in_stride, out_stride, resets=None):
+        """pv_glide_process_device on raw device pointers (ints), asynchronous on the handle's stream; hops / resets are host rows."""
+        h, r, rstride = self._rows(hops, resets)
+        rp = r.ctypes.data_as(C.POINTER(C.c_uint8)) if r is not None else None
+        self._check(self._L.pv_glide_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, h.size, h.ctypes.data_as(C.POINTER(C.c_int32)), rp, rstride,
+                                                    in_stride, out_stride))

@@ -1,5 +1,5 @@
-// pv_host_common.h -- what the host sides of the four handle types (pv_capi.hip, stretch/pv_stretch_capi.hip, resample/pv_resample_capi.hip,
-// resample/pv_pitch_capi.hip) share: error reporting, the liveness check, the HIP check macros, the device buffer that grows on demand and the
+// pv_host_common.h -- what the host sides of the six handle types (pv_capi.hip, stretch/pv_stretch_capi.hip, resample/pv_resample_capi.hip,
+// resample/pv_pitch_capi.hip, resample/pv_vari_capi.hip, resample/pv_glide_capi.hip) share: error reporting, the liveness check, the HIP check macros, the device buffer that grows on demand and the
 // twiddle / window tables.  Host code only; everything here is generic over the handle struct H, which has `magic`, `err` and `stream` members.
 // It lives in host/ so that the identity of the kernel sources (every *.hip and *.h directly in csrc/, bench.py) does not move with a host-only edit.
 #pragma once
@@ -17,7 +17,7 @@
 namespace {
 
 // One specialisation per handle type (PV_HOST_HANDLE, once in its file): its magic word, its destroy entry point, and the thread-local buffer that
-// holds the error of a failed create, where no handle exists yet (as large as the handle's own `err`).  The four buffers are independent of each
+// holds the error of a failed create, where no handle exists yet (as large as the handle's own `err`).  The buffers are independent of each
 // other.  kNoHandle is what a create function passes to fail / failf to report there.
 template <class H> struct HostTraits;
 

@@ -12,8 +12,11 @@ three more at hop 320 = hs), with its ratio to the tempo line; the strength line
 The resample lines (pv_resample_process_device) take the mono 1024 shape's stretched length, frames * 320 samples, down by 4/5 (taps in LDS) and by
 147/160; their `hbm_fraction` is (M / L + 1) * 4 B per output against 8 TB/s.  The pitch line (pv_pitch_process_device) is the mono 1024 shape, 256 -> 320
 and then 4/5, with its ratio to the stretch line of the same shape.
+With --vari: the variable-ratio resampler (pv_vari_process_device) on the same stretched length in blocks of 320, once with counts alternating 256 /
+257 (the fixed 4/5 line's neighbour) and once on a 200 .. 400 ramp, and the pitch-curve handle (pv_glide_process_device) on the mono 1024 shape with
+the same two hop rows, with its ratio to the stretch line.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari]
 """
 import argparse
 import json
@@ -135,6 +138,43 @@ def pitch_stretch_line(torch, phaze_amd, N, ha, hs, T, steps, warmup):
             "ms_per_launch": round(ms, 4), "frames_per_s": T / (ms * 1e-3), "hbm_fraction": T * (ha + hs * L / M) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def _vari_counts(kind, T):
+    if kind == "alternating 256 / 257":
+        return (256 + (np.arange(T) & 1)).astype(np.int32)
+    return np.round(np.linspace(200, 400, T)).astype(np.int32)
+
+
+def vari_line(torch, phaze_amd, kind, B, T, steps, warmup):
+    counts = _vari_counts(kind, T)
+    total = int(counts.astype(np.int64).sum())
+    rs = phaze_amd.VariResampler(B, 200, 400, max_channels=1, max_blocks=1)
+    x = (torch.rand((1, T * B), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, total), device="cuda")
+    stream = torch.cuda.Stream()
+    rs.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: rs.process_device(x.data_ptr(), 1, counts, T * B, y.data_ptr(), total, total), steps, warmup)
+    taps = rs.taps
+    rs.close()
+    return {"kernel": "pv_vari", "schedule": kind, "block": B, "taps": taps, "channels": 1, "input_samples": T * B, "ms_per_launch": round(ms, 4),
+            "outputs_per_s": total / (ms * 1e-3), "hbm_fraction": (T * B + total) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
+def glide_line(torch, phaze_amd, kind, N, hs, T, steps, warmup):
+    hops = _vari_counts(kind, T)
+    total = int(hops.astype(np.int64).sum())
+    p = phaze_amd.PitchGlide(N, hs, 200, 400, max_channels=1, max_frames=T)
+    x = (torch.rand((1, total), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, total), device="cuda")
+    stream = torch.cuda.Stream()
+    p.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: p.process_device(x.data_ptr(), y.data_ptr(), 1, hops, total, total), steps, warmup)
+    p.close()
+    return {"kernel": "pv_glide", "schedule": kind, "fft": N, "synthesis_hop": hs, "channels": 1, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
+            "frames_per_s": T / (ms * 1e-3), "samples_per_s": total / (ms * 1e-3), "hbm_fraction": 2 * total * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -161,6 +201,7 @@ def main():
     ap.add_argument("--no-link", action="store_true", help="skip the linked-channel lines")
     ap.add_argument("--no-transient", action="store_true", help="skip the reset line and the onset-strength line")
     ap.add_argument("--no-resample", action="store_true", help="skip the two resample lines and the pitch-through-the-stretch line")
+    ap.add_argument("--vari", action="store_true", help="add the variable-ratio resampler lines and the pitch-curve lines")
     args = ap.parse_args()
     import torch
     import phaze_amd
@@ -192,6 +233,13 @@ def main():
         r = pitch_stretch_line(torch, phaze_amd, 1024, 256, 320, T, args.steps, args.warmup)
         r["ratio_to_stretch"] = round(r["frames_per_s"] / unlinked[(1024, 1)], 4)
         print(json.dumps(r), flush=True)
+    if args.vari:
+        for kind in ("alternating 256 / 257", "ramp 200 .. 400"):
+            print(json.dumps(vari_line(torch, phaze_amd, kind, 320, T, args.steps, args.warmup)), flush=True)
+        for kind in ("alternating 256 / 257", "ramp 200 .. 400"):
+            r = glide_line(torch, phaze_amd, kind, 1024, 320, T, args.steps, args.warmup)
+            r["ratio_to_stretch"] = round(r["frames_per_s"] / unlinked[(1024, 1)], 4)
+            print(json.dumps(r), flush=True)
     if not args.no_compare:
         print(json.dumps(pitch_line(torch, phaze_amd, "pitch headline, same input", 1024, 256, 1, T, 1.5, args.steps, args.warmup)), flush=True)
         # --speed 1.25: 0.8x as many input frames after the host resampler, pitch 1 / 1.25: the same output duration as the 1.25x stretch above

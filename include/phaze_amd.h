@@ -53,7 +53,8 @@ typedef struct pv_handle pv_handle;
  *     layout or semantic change): variable tempo on that handle, pv_tempo_process / pv_tempo_process_device; linked channels,
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
- *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*. */
+ *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
+ *     pv_tune_plan. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -581,6 +582,78 @@ PV_API int pv_glide_process_device(pv_glide *h, const float *d_in, float *d_out,
  * them another stream, or process through them directly. */
 PV_API pv_stretch *pv_glide_stretch(pv_glide *h);
 PV_API pv_vari *pv_glide_resampler(pv_glide *h);
+
+/* ---- pitch tracking and pitch correction: an f0 tracker (a separate handle) and the planner of glide rows ------------------------------- */
+/* YIN on block-scaled integers: every value of a record is an exact integer function of the frame's samples, whatever the tiling.  Per channel,
+ * frame m reads the W + max_lag samples x[m hop, m hop + W + max_lag) and nothing else: no padding, no carried state; a stream analysed in pieces
+ * overlaps them by W + max_lag - hop samples.  16 <= W <= 4096, 2 <= min_lag < max_lag <= 4096, 1 <= hop <= 4096.
+ *   scale    A = max |x_i| in f32; a non-finite sample or A == 0 gives the record {0, 0, 0, 0}.  Else A = f 2^e with f in [0.5, 1) and
+ *            q_i = rint(x_i 2^(11 - e)), exactly scaled, ties to even: |q_i| <= 2048.
+ *   d(tau)   = sum_{i < W} (q_i - q_{i+tau})^2 for tau = 1 .. max_lag (<= 2^36).
+ *   c(tau)   = (d(tau) tau 2^14) div cum(tau) in int64, cum(tau) = d(1) + .. + d(tau); 2^14 where cum(tau) == 0, and c(0) = 2^14.
+ *   pick     the smallest tau in [min_lag, max_lag - 1] with c(tau) < threshold, advanced while tau < max_lag - 1 and c(tau + 1) < c(tau): the record
+ *            is {tau, c(tau - 1), c(tau), c(tau + 1)}.  No such tau: the frame is unvoiced, b is the first argmin of c over [min_lag, max_lag - 1] and
+ *            the record is {-b, c(b - 1), c(b), c(b + 1)}.
+ * A record is four int32.  threshold is per call, in [1, 16384] in units of 2^-14 (2458 is about 0.15). */
+typedef struct pv_f0_config {
+    int32_t struct_size;     /* sizeof(pv_f0_config) as the caller compiled it (PV_F0_CONFIG_INIT sets it)                        */
+    int32_t window;          /* W, the samples summed per lag                                                                    */
+    int32_t hop;             /* samples between frames                                                                           */
+    int32_t min_lag;         /* the shortest period looked for                                                                   */
+    int32_t max_lag;         /* the lags computed; the longest period looked for is max_lag - 1                                  */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_frames;      /* host-pointer calls: staging size in frames (0 => 256); longer calls go in pieces                 */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_f0_config;
+#define PV_F0_CONFIG_INIT { (int32_t)sizeof(pv_f0_config), 0, 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_f0 pv_f0;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_f0_last_error(NULL). */
+PV_API int pv_f0_create(const pv_f0_config *cfg, pv_f0 **out);
+PV_API int pv_f0_destroy(pv_f0 *h);
+PV_API const char *pv_f0_last_error(const pv_f0 *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_f0_set_stream(pv_f0 *h, void *hip_stream);
+PV_API int pv_f0_synchronize(pv_f0 *h);
+/* nframes frames of channels 0 .. nch-1: channel c reads in[c*in_stride .. + (nframes - 1) hop + W + max_lag) and writes nframes records to
+ * records[4 (c*rec_stride + m) ..): rec_stride counts records.  Rejected with PV_ERR_ARGUMENT before any device work: a null buffer, a negative count,
+ * a threshold outside [1, 16384] and, with nch > 1, strides below what a channel reads and writes.  nch > max_channels: PV_ERR_CAPACITY.  Host
+ * pointers, synchronous, staged in pieces of max_frames. */
+PV_API int pv_f0_track(pv_f0 *h, const float *in, int32_t nch, int64_t nframes, int64_t in_stride, int32_t threshold, int32_t *records, int64_t rec_stride);
+/* The same on DEVICE in / records pointers (records 16-byte aligned: a record is one store), asynchronous on the handle's stream. */
+PV_API int pv_f0_track_device(pv_f0 *h, const float *d_in, int32_t nch, int64_t nframes, int64_t in_stride, int32_t threshold, int32_t *d_records,
+                              int64_t rec_stride);
+/* Pure host code.  The period of one record in samples, fp64: tau + 0.5 (c- - c+) / (c- - 2 c0 + c+) when that denominator is positive, else tau;
+ * 0 for an unvoiced or empty record. */
+PV_API double pv_f0_period(const int32_t rec[4]);
+
+/* Pitch correction onto a scale: from one channel's records to the hop row of pv_glide_process.  Frame by frame, with S the input consumed so far:
+ * the record j = clamp((S + shift - f0_center + f0_hop div 2) div f0_hop, 0, nrec - 1) (floor division) has the period p; when p > 0,
+ * n = 69 + 12 log2(sample_rate / p / a4), n* is the allowed note nearest n (ties to the lower) and t = strength (n* - n) / 12, else t = 0.  Then
+ * r += retune (t - r), x = e + synthesis_hop / 2^r, hop = clamp(floor(x + 0.5), min_hop, max_hop), e = x - hop (the error diffusion of the bindings'
+ * tempo_hops); the plan ends before the frame with S + hop > input_len. */
+typedef struct pv_tune_params {
+    int32_t struct_size;     /* sizeof(pv_tune_params) as the caller compiled it (PV_TUNE_PARAMS_INIT sets it)                    */
+    int32_t f0_hop;          /* the tracker's hop                                                                                */
+    int32_t f0_center;       /* where in its span a record is taken to sit, normally (W + max_lag) / 2                           */
+    int32_t scale_mask;      /* 12 bits, bit k = pitch class k is allowed, C = 0; 0xFFF is chromatic; 0 is an error              */
+    int32_t synthesis_hop;   /* the glide's                                                                                      */
+    int32_t min_hop;         /* the glide's                                                                                      */
+    int32_t max_hop;         /* the glide's                                                                                      */
+    int32_t reserved;        /* must be 0                                                                                        */
+    double sample_rate;      /* in Hz                                                                                            */
+    double a4;               /* the reference pitch of note 69 in Hz; 0 => 440                                                   */
+    double strength;         /* 0 .. 1: how much of the way to the note                                                          */
+    double retune;           /* (0, 1]: the one-pole speed per frame, 1 jumps                                                    */
+    int64_t input_len;       /* samples per channel of the input                                                                 */
+    int64_t shift;           /* the caller's compensation for the glide's content lag, in input samples; may be 0                */
+} pv_tune_params;
+#define PV_TUNE_PARAMS_INIT { (int32_t)sizeof(pv_tune_params), 0, 0, 0xFFF, 0, 0, 0, 0, 0.0, 440.0, 1.0, 1.0, 0, 0 }
+/* Returns the number of frames planned and writes at most `capacity` of them (the two-call sizing of pv_transient_plan): hops[m], and when curve is
+ * not NULL the shift r of frame m in octaves.  records: nrec records of one channel, contiguous.  -PV_ERR_ARGUMENT for an argument out of range. */
+PV_API int64_t pv_tune_plan(const pv_tune_params *p, const int32_t *records, int64_t nrec, int32_t *hops, double *curve, int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,8 @@ EXPORTS = [
     "pv_vari_process", "pv_vari_process_device", "pv_vari_export_state", "pv_vari_import_state", "pv_vari_prototype", "pv_vari_half_width",
     "pv_glide_create", "pv_glide_destroy", "pv_glide_reset", "pv_glide_last_error", "pv_glide_set_stream", "pv_glide_synchronize",
     "pv_glide_process", "pv_glide_process_device", "pv_glide_stretch", "pv_glide_resampler",
+    "pv_f0_create", "pv_f0_destroy", "pv_f0_last_error", "pv_f0_set_stream", "pv_f0_synchronize", "pv_f0_track", "pv_f0_track_device", "pv_f0_period",
+    "pv_tune_plan",
 ]
 
 
@@ -70,6 +72,25 @@ class _VariConfig(C.Structure):
 
 class _GlideConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "fft_size", "synthesis_hop", "min_hop", "max_hop", "max_channels", "max_frames", "device_id", "flags")]
+
+
+class _F0Config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "window", "hop", "min_lag", "max_lag", "max_channels", "max_frames", "device_id", "flags")]
+
+
+class _TuneParams(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "f0_hop", "f0_center", "scale_mask", "synthesis_hop", "min_hop", "max_hop", "reserved")]
+                + [(n, C.c_double) for n in ("sample_rate", "a4", "strength", "retune")] + [(n, C.c_int64) for n in ("input_len", "shift")])
+
+
+def make_f0_config(window, hop, min_lag, max_lag, max_channels=1, max_frames=0, device_id=0, flags=0):
+    """pv_f0_config with struct_size filled in (the C side's PV_F0_CONFIG_INIT)."""
+    return _F0Config(C.sizeof(_F0Config), window, hop, min_lag, max_lag, max_channels, max_frames, device_id, flags)
+
+
+def make_tune_params(f0_hop, f0_center, sample_rate, synthesis_hop, min_hop, max_hop, input_len, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0, shift=0):
+    """pv_tune_params with struct_size filled in (the C side's PV_TUNE_PARAMS_INIT)."""
+    return _TuneParams(C.sizeof(_TuneParams), f0_hop, f0_center, scale_mask, synthesis_hop, min_hop, max_hop, 0, sample_rate, a4, strength, retune, input_len, shift)
 
 
 def make_vari_config(block, min_count, max_count, max_channels=1, max_blocks=0, device_id=0, flags=0):
@@ -242,6 +263,15 @@ def load_library():
     L.pv_glide_process_device.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, ip, bp, C.c_int64, C.c_int64, C.c_int64]
     L.pv_glide_stretch.argtypes = [vp]
     L.pv_glide_resampler.argtypes = [vp]
+    L.pv_f0_create.argtypes = [C.POINTER(_F0Config), C.POINTER(vp)]
+    L.pv_f0_destroy.argtypes = [vp]
+    L.pv_f0_last_error.argtypes = [vp]
+    L.pv_f0_set_stream.argtypes = [vp, vp]
+    L.pv_f0_synchronize.argtypes = [vp]
+    L.pv_f0_track.argtypes = [vp, fp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64]
+    L.pv_f0_track_device.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64]
+    L.pv_f0_period.argtypes = [ip]
+    L.pv_tune_plan.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, ip, C.POINTER(C.c_double), C.c_int64]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -253,6 +283,9 @@ def load_library():
     L.pv_vari_half_width.restype = C.c_int32
     L.pv_vari_last_error.restype = L.pv_glide_last_error.restype = C.c_char_p
     L.pv_glide_stretch.restype = L.pv_glide_resampler.restype = vp
+    L.pv_f0_last_error.restype = C.c_char_p
+    L.pv_f0_period.restype = C.c_double
+    L.pv_tune_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -314,7 +347,7 @@ class _Handle:
         self._L = load_library()
         self._h = C.c_void_p(handle)
         self._destroy, self._last_error, self._reset, self._set_stream, self._synchronize = (
-            getattr(self._L, f"{self._prefix}_{n}") for n in ("destroy", "last_error", "reset", "set_stream", "synchronize"))
+            getattr(self._L, f"{self._prefix}_{n}", None) for n in ("destroy", "last_error", "reset", "set_stream", "synchronize"))   # a stateless handle has no reset
 
     def _create(self, cfg):
         self._bind()
@@ -1139,3 +1172,96 @@ class PitchGlide(_Handle):
         rp = r.ctypes.data_as(C.POINTER(C.c_uint8)) if r is not None else None
         self._check(self._L.pv_glide_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), nch, h.size, h.ctypes.data_as(C.POINTER(C.c_int32)), rp, rstride,
                                                     in_stride, out_stride))
+
+    def process_tuned(self, x, sample_rate, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0, shift=0):
+        """Offline pitch correction onto a scale, the counterpart of TimeStretch.process_transients: F0Tracker.track (channel 0: the glide has one row
+        for all channels) -> tune_plan -> process.  x: float32[nch, n] (host).  tracker: an F0Tracker, default window = max_lag = fft_size, hop =
+        synthesis_hop, min_lag = 32.  shift: the caller's compensation for the content lag, in input samples.  Returns (y of the shape of
+        x[:, :hops.sum()], hops)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        own = tracker is None
+        if own:
+            tracker = F0Tracker(min(self.fft_size, 4096), self.synthesis_hop, 32, min(self.fft_size, 4096))
+        try:
+            records = tracker.track(x[0], threshold)[0]
+        finally:
+            if own:
+                tracker.close()
+        hops = tune_plan(records, tracker.hop, sample_rate, self.synthesis_hop, self.min_hop, self.max_hop, x.shape[1], scale_mask=scale_mask, strength=strength,
+                         retune=retune, a4=a4, shift=shift, f0_center=(tracker.window + tracker.max_lag) // 2)
+        y = self.process(x[:, :int(hops.astype(np.int64).sum())], hops)
+        return (y[0] if one else y), hops
+
+
+def f0_period(records):
+    """pv_f0_period: float64 periods in samples of int32[..., 4] records (F0Tracker.track); 0 for an unvoiced or empty record."""
+    L = load_library()
+    r = np.ascontiguousarray(records, dtype=np.int32)
+    if r.ndim < 1 or r.shape[-1] != 4:
+        raise ValueError("records must be int32[..., 4]")
+    flat = r.reshape(-1, 4)
+    out = np.empty(flat.shape[0], np.float64)
+    ip = C.POINTER(C.c_int32)
+    for i in range(flat.shape[0]):
+        out[i] = L.pv_f0_period(flat[i].ctypes.data_as(ip))
+    return out.reshape(r.shape[:-1])
+
+
+def tune_plan(records, f0_hop, sample_rate, synthesis_hop, min_hop, max_hop, input_len, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0, shift=0,
+              f0_center=0, curve=False):
+    """pv_tune_plan: the int32 hop row of PitchGlide.process that moves every frame onto the nearest allowed note.  records: int32[nrec, 4] of ONE
+    channel; scale_mask: bit k = pitch class k (C = 0); strength 0 .. 1; retune (0, 1], the one-pole speed per frame; f0_center: where in its span a
+    record sits, normally (window + max_lag) // 2.  curve=True returns (hops, float64 shift per frame in octaves)."""
+    L = load_library()
+    r = np.ascontiguousarray(records, dtype=np.int32)
+    if r.size and (r.ndim != 2 or r.shape[1] != 4):
+        raise ValueError("records must be int32[nrec, 4]: one channel")
+    nrec = r.shape[0] if r.size else 0
+    p = make_tune_params(f0_hop, f0_center, float(sample_rate), synthesis_hop, min_hop, max_hop, int(input_len), scale_mask, float(strength), float(retune), float(a4),
+                         int(shift))
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rp = r.ctypes.data_as(ip) if nrec else None
+    n = L.pv_tune_plan(C.byref(p), rp, nrec, None, None, 0)
+    if n < 0:
+        raise ValueError("tune_plan: bad argument (scale_mask 1 .. 0xFFF, strength 0 .. 1, retune (0, 1], 1 <= min_hop <= max_hop, positive rates)")
+    hops, r_row = np.zeros(n, np.int32), np.zeros(n, np.float64)
+    if n:
+        L.pv_tune_plan(C.byref(p), rp, nrec, hops.ctypes.data_as(ip), r_row.ctypes.data_as(dp), n)
+    return (hops, r_row) if curve else hops
+
+
+class F0Tracker(_Handle):
+    """The fundamental-frequency tracker (pv_f0_*): YIN on block-scaled integers.  Frame m of a channel reads x[m hop, m hop + window + max_lag) and
+    gives one record int32[4] = {lag, c(lag - 1), c(lag), c(lag + 1)}, lag < 0 for an unvoiced frame and all zeros for silence or a non-finite sample;
+    f0_period turns records into periods.  Stateless: a stream analysed in pieces overlaps them by window + max_lag - hop samples."""
+
+    _prefix = "pv_f0"
+
+    def __init__(self, window, hop, min_lag, max_lag, max_channels=1, max_frames=0, device_id=0):
+        self._create(make_f0_config(window, hop, min_lag, max_lag, max_channels, max_frames, device_id, 0))
+        self.window, self.hop, self.min_lag, self.max_lag, self.max_channels = window, hop, min_lag, max_lag, max_channels
+
+    def reset(self):
+        """Nothing to reset: the tracker carries no state."""
+
+    def frames(self, n):
+        """How many frames fit n samples per channel."""
+        return max((n - self.window - self.max_lag) // self.hop + 1, 0)
+
+    def track(self, x, threshold=2458):
+        """x: float32[nch, n] (host) -> int32[nch, frames(n), 4]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        nframes = self.frames(n)
+        rec = np.zeros((nch, nframes, 4), np.int32)
+        self._check(self._L.pv_f0_track(self._h, _fp(x), nch, nframes, n, int(threshold), rec.ctypes.data_as(C.POINTER(C.c_int32)), nframes))
+        return rec
+
+    def track_device(self, d_in, nch, nframes, in_stride, d_records, rec_stride, threshold=2458):
+        """pv_f0_track_device on raw device pointers (ints), asynchronous on the handle's stream; rec_stride counts records."""
+        self._check(self._L.pv_f0_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, int(threshold), C.c_void_p(d_records), rec_stride))

@@ -40,3 +40,8 @@ hipError_t pv_launch_stretch(int log2n, const PvStretchParams &p, int G, const i
 // samples), one workgroup per (chain of F frames, group); stateless
 hipError_t pv_launch_onset_strength(int log2n, const float *in, long in_stride, int nch, int G, int nframes, int ha, int F, const double2 *tw64,
                                     const float *hann, int *counts, long count_stride, hipStream_t st);
+// the f0 tracker (pv_f0_kernels.hip): records[(c * rec_stride + m) * 4 ..) = {lag, c(lag - 1), c(lag), c(lag + 1)} of frame m of channel c, which reads
+// in[c * in_stride + m * hop, + W + max_lag); one workgroup per (frame, channel); stateless.  records is 16-byte aligned, rec_stride counts records
+hipError_t pv_launch_f0(const float *in, long in_stride, int nch, int nframes, int W, int hop, int min_lag, int max_lag, int threshold, int *records,
+                        long rec_stride, hipStream_t st);
+size_t pv_f0_lds_bytes(int W, int max_lag);

@@ -15,8 +15,10 @@ and then 4/5, with its ratio to the stretch line of the same shape.
 With --vari: the variable-ratio resampler (pv_vari_process_device) on the same stretched length in blocks of 320, once with counts alternating 256 /
 257 (the fixed 4/5 line's neighbour) and once on a 200 .. 400 ramp, and the pitch-curve handle (pv_glide_process_device) on the mono 1024 shape with
 the same two hop rows, with its ratio to the stretch line.
+With --f0: only the f0 tracker (pv_f0_track_device) at W = 1024, max_lag = 1024, hop = 256, lags from 32, mono and 8 channels, --f0-frames frames per
+channel of a harmonic tone; frames/s counts channel-frames, and `macs_per_s` is frames/s times the W * max_lag multiply-adds of a frame's lag products.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]]
 """
 import argparse
 import json
@@ -175,6 +177,24 @@ def glide_line(torch, phaze_amd, kind, N, hs, T, steps, warmup):
             "frames_per_s": T / (ms * 1e-3), "samples_per_s": total / (ms * 1e-3), "hbm_fraction": 2 * total * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def f0_line(torch, phaze_amd, W, hop, lo, ML, nch, T, steps, warmup):
+    n = (T - 1) * hop + W + ML
+    k = torch.arange(n, device="cuda", dtype=torch.float32)
+    x = torch.stack([sum(torch.sin(2 * np.pi * h * k / (217.3 + 31 * c)) / h for h in range(1, 6)) for c in range(nch)]).contiguous() * 0.3
+    rec = torch.empty((nch, T, 4), dtype=torch.int32, device="cuda")
+    trk = phaze_amd.F0Tracker(W, hop, lo, ML, max_channels=nch, max_frames=1)
+    stream = torch.cuda.Stream()
+    trk.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: trk.track_device(x.data_ptr(), nch, T, n, rec.data_ptr(), T), steps, warmup)
+    trk.close()
+    voiced = int((rec[:, :, 0] > 0).sum().item())
+    frames = nch * T
+    return {"kernel": "pv_f0", "window": W, "hop": hop, "min_lag": lo, "max_lag": ML, "channels": nch, "frames_per_channel": T, "voiced_frames": voiced,
+            "ms_per_launch": round(ms, 4), "frames_per_s": frames / (ms * 1e-3), "macs_per_frame": W * ML, "macs_per_s": frames * W * ML / (ms * 1e-3),
+            "hbm_fraction": frames * (hop * 4 + 16) / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -202,9 +222,15 @@ def main():
     ap.add_argument("--no-transient", action="store_true", help="skip the reset line and the onset-strength line")
     ap.add_argument("--no-resample", action="store_true", help="skip the two resample lines and the pitch-through-the-stretch line")
     ap.add_argument("--vari", action="store_true", help="add the variable-ratio resampler lines and the pitch-curve lines")
+    ap.add_argument("--f0", action="store_true", help="only the f0 tracker lines")
+    ap.add_argument("--f0-frames", type=int, default=16384, help="frames per channel of the f0 lines")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.f0:
+        for nch in (1, 8):
+            print(json.dumps(f0_line(torch, phaze_amd, 1024, 256, 32, 1024, nch, args.f0_frames, args.steps, args.warmup)), flush=True)
+        return
     T = args.frames
     shapes = [(1024, 256, 320, 1, T), (2048, 512, 640, 2, T // 2), (4096, 1024, 1280, 8, T // 8)]
     unlinked = {}

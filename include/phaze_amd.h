@@ -349,6 +349,8 @@ PV_API int pv_transient_process_device(pv_stretch *h, const float *d_in, float *
  * zeros.  counts[g * count_stride + m] = the number of bins k in [1, N/2) with mag_m[k] > 4 * mag_{m-1}[k] and mag_m[k] > 2^-20 * max_k mag_m, for
  * group g (slot g when unlinked) of in[c * in_stride .. + nframes * analysis_hop).  A pure function of the buffer: it neither reads nor writes the
  * handle's carried state.  A stream analysed in pieces overlaps them by N + analysis_hop samples and drops the frames that saw the padding.
+ * Non-finite input: a comparison with a NaN or between two infinities is false, so counts is 0 on every frame whose window holds a NaN or +-Inf
+ * sample and on the first frame after those (its previous magnitudes are not finite); every other frame is untouched.
  * Thresholds and peak picking stay with the caller (pv_onsets_from_strength).  Host pointers, synchronous. */
 PV_API int pv_onset_strength(pv_stretch *h, const float *in, int32_t nch, int32_t nframes, int64_t in_stride, int32_t *counts,
                              int64_t count_stride);
@@ -392,7 +394,9 @@ PV_API int pv_onset_chain_layout(pv_stretch *h, int32_t nch, int32_t nframes, in
  * accumulated in f32 in the order i = 0, 1, .. T - 1 with one fused multiply-add per tap, whatever the tiling.  After I input samples in total exactly
  * J(I) = max(0, ceil((I - W) L / M)) outputs exist: a call that takes the total from I0 to I1 writes J(I1) - J(I0) samples per channel, all channel slots
  * of a handle move together, the output lags by W input samples, and W zeros drain the stream.  The carried state is the newest T - 1 input samples per
- * slot and the int64 pair (I, J): copies of input and integers, so any split of a stream into calls gives the same bits.  Replaces what the reference
+ * slot and the int64 pair (I, J): copies of input and integers, so any split of a stream into calls gives the same bits.  Non-finite input: every
+ * output runs all T taps of its phase row, a tap that is 0 included (0 * NaN is NaN), so output j is NaN or +-Inf exactly when one of the T samples
+ * x[n_j - W + 1 .. n_j + W] is -- unlike pv_vari, whose zero-weight taps read nothing.  T - 1 clean samples flush the history.  Replaces what the reference
  * leaves to the browser's player (playbackRate, /root/reference/src/main.js:75-96).  See INTEGRATION.md "Pitch". */
 typedef struct pv_resample_config {
     int32_t struct_size;     /* sizeof(pv_resample_config) as the caller compiled it (PV_RESAMPLE_CONFIG_INIT sets it)           */
@@ -493,7 +497,11 @@ PV_API pv_resample *pv_pitch_resampler(pv_pitch *h);
  * both sums in f32 with i ascending (one fused multiply-add and one add per tap), then one f32 division: unit DC gain at every position and ratio,
  * and the same bits whatever the tiling.  The output lags by W input samples; every output of a block is computable once the block is in, so a call
  * of nblocks blocks consumes nblocks * B samples per channel and writes sum(counts).  The carried state is the newest T - 1 input samples per slot;
- * the int64 counters (blocks, outputs) are informational.  All channel slots of a handle move together.  See INTEGRATION.md "Pitch curves". */
+ * the int64 counters (blocks, outputs) are informational.  All channel slots of a handle move together.  See INTEGRATION.md "Pitch curves".
+ * Non-finite input: a tap whose weight is exactly 0 leaves the sums as they are whatever its sample holds, so output j is NaN or +-Inf exactly when a
+ * NaN or +-Inf input sample, carried history included, lies under a tap of j with w_i != 0 (within 32 max(1, B / c) samples of its position); every
+ * other output has the value it would have with those samples replaced by 0, in every split of the stream into calls.  The history carries the samples
+ * as they came: T - 1 clean samples flush it. */
 typedef struct pv_vari_config {
     int32_t struct_size;     /* sizeof(pv_vari_config) as the caller compiled it (PV_VARI_CONFIG_INIT sets it)                   */
     int32_t block;           /* B, input samples per block                                                                       */

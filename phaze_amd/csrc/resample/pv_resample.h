@@ -4,6 +4,9 @@
 // j M / L = n_j + phase_j / L and is  y[j] = sum_{i < T} h[phase_j][i] x[n_j - W + 1 + i].
 // SUMMATION ORDER (part of the contract: any tiling gives the same bits): one f32 accumulator, acc = 0, then for i = 0, 1, .. T - 1 in this order
 // acc = fmaf(h[phase_j][i], x[n_j - W + 1 + i], acc).  The order is a function of i alone.
+// NON-FINITE INPUT: every output runs all T taps, a tap that is 0 included, and fmaf(0, NaN, acc) is NaN: output j is non-finite exactly when one of
+// the T samples x[n_j - W + 1 .. n_j + W] is, carried history included.  Which taps run does not depend on the tiling, so this is the same in every
+// split of a stream into calls.  (pv_vari.h has the other rule: there a launch may skip zero-weight taps, so such a tap must read nothing.)
 //
 // One launch covers `nout` outputs of `nch` channels, one workgroup per (tile of `tile` outputs, channel).  Everything the kernel indexes with is
 // relative to the call: input index r means in[r] for r >= 0 and hist[T - 1 + r] for r < 0 (the carried newest T - 1 samples).  The host passes the

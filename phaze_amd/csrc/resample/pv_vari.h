@@ -8,6 +8,11 @@
 // SUMMATION ORDER (part of the contract: any tiling gives the same bits): num = den_sum = 0, then for i ascending num = fmaf(w_i, x_i, num) and
 // den_sum = den_sum + w_i, then one IEEE f32 division.  A tap whose weight is exactly 0 leaves both sums as they are, so a launch may skip the taps
 // that are 0 for every output of a tile: only i in [W - g, W + g - 1], g = ceil(32 den / c), can be non-zero.
+// NON-FINITE INPUT (part of the contract for the same reason: any tiling, and so any split of a stream into calls, gives the same bits).  A tap whose
+// weight is exactly 0 does not touch num WHATEVER its sample holds: fmaf(0, NaN, num) and fmaf(0, Inf, num) are NaN, so a tile whose staged span
+// holds a non-finite sample selects on w != 0 instead of relying on the product (a clean span keeps the bare multiply-add: the same bits).  Hence: output j is non-finite exactly when a non-finite input sample, carried history included, lies under a
+// tap of j whose weight w_i, in the arithmetic above, is non-zero; every other output has the value it would have with those samples replaced by 0.
+// (pv_resample.h has the other rule: it runs all T taps of a phase row for every output, zero ones included.)
 // (q, rem) is formed incrementally: a Q moves by c Q per tap, so the pair moves by (c Q div den, c Q mod den) with a carry; exact integers, a Q < 2^30.
 //
 // One launch covers `nout` outputs of `nch` channels, one workgroup per (tile of `tile` consecutive outputs of the call, channel).  Everything the

@@ -7,6 +7,7 @@
 // index ascending.  Per output: a search for its
 // block in the LDS slice, three integer divisions (position, the per-tap step of the table index, the index of the first tap), then per tap only
 // adds, compares and selects on the index pair, two table reads, one input read and three floating-point operations.
+// A tile whose span holds a NaN or an Inf (found while staging) takes a second copy of the tap loops that skips zero-weight taps in the numerator.
 // The history roll is pv_resample_history (pv_resample_kernels.hip), launched by the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,11 +26,57 @@ __device__ __forceinline__ float weight(const float *P, int q, int rem, float in
     return fmaf((float)rem * inv, p1 - p0, p0);
 }
 
+// one tap of the numerator.  A weight of exactly 0 leaves the sum as it is whatever the sample holds (0 * NaN and 0 * Inf are NaN): which zero taps a
+// launch runs depends on the tile, so they must not show in the output (pv_vari.h, NON-FINITE INPUT).  GUARD = false is for a tile whose staged span
+// holds finite samples only, where the bare multiply-add gives the same bits.
+template <bool GUARD>
+__device__ __forceinline__ float tap(float w, float x, float num)
+{
+    return (!GUARD || w != 0.0f) ? fmaf(w, x, num) : num;
+}
+
+__device__ __forceinline__ bool non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// the taps of a thread's R outputs, tap index ascending; (q, rem) arrives standing for tap i_lo
+template <int R, bool GUARD>
+__device__ __forceinline__ void run_taps(const float *P, const float *xs, int i_lo, int W, int i_hi, const int (&off)[R], const float (&inv)[R], const int (&den)[R],
+                                         const int (&dq)[R], const int (&dr)[R], int (&q)[R], int (&rem)[R], float (&num)[R], float (&sum)[R])
+{
+    // taps at or before the output position: a falls by c per tap
+    for (int i = i_lo; i < W; i++) {
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const float w = weight(P, q[k], rem[k], inv[k]);
+            num[k] = tap<GUARD>(w, xs[lds_word(off[k] + i)], num[k]);
+            sum[k] += w;
+            q[k] -= dq[k]; rem[k] -= dr[k];
+            if (rem[k] < 0) { rem[k] += den[k]; q[k] -= 1; }
+        }
+    }
+    // (q, rem) now stands for a Q = (r - c) Q < 0, floored; tap W has a = c - r
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        q[k] = rem[k] == 0 ? -q[k] : -q[k] - 1;
+        rem[k] = rem[k] == 0 ? 0 : den[k] - rem[k];
+    }
+    // taps behind the output position: a grows by c per tap
+    for (int i = W; i <= i_hi; i++) {
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const float w = weight(P, q[k], rem[k], inv[k]);
+            num[k] = tap<GUARD>(w, xs[lds_word(off[k] + i)], num[k]);
+            sum[k] += w;
+            q[k] += dq[k]; rem[k] += dr[k];
+            if (rem[k] >= den[k]) { rem[k] -= den[k]; q[k] += 1; }
+        }
+    }
+}
+
 template <int R>
 __global__ __launch_bounds__(PV_VARI_THREADS) void pv_vari_kernel(PvVariParams p)
 {
     extern __shared__ float4 lds4[];
-    __shared__ int s_minc;
+    __shared__ int s_minc, s_bad;                               // the tile's smallest count; whether its span holds a NaN or an Inf
     float *xs = (float *)lds4;
     int *ps = (int *)(xs + pv_vari_span_words(p.span));
     float *P = (float *)(ps + pv_vari_prefix_words(p.tile));
@@ -40,7 +87,7 @@ __global__ __launch_bounds__(PV_VARI_THREADS) void pv_vari_kernel(PvVariParams p
     const int2 tb = p.tile_blocks[blockIdx.x];
     const int b0 = tb.x, nb = tb.y - tb.x + 1;                  // 1 <= nb <= tile: every block holds at least one output
 
-    if (tid == 0) s_minc = 0x7fffffff;
+    if (tid == 0) { s_minc = 0x7fffffff; s_bad = 0; }
     __syncthreads();
     for (int j = tid; j <= nb; j += PV_VARI_THREADS) {
         const int v = p.prefix[b0 + j];
@@ -59,7 +106,12 @@ __global__ __launch_bounds__(PV_VARI_THREADS) void pv_vari_kernel(PvVariParams p
     const int hb = T - 1 + r0;                                  // history index of e = 0
     const int e_in0 = min(span, max(0, -r0));
     const int e_in1 = max(e_in0, min(span, p.nin - r0));
-    for (int e = tid; e < e_in0; e += PV_VARI_THREADS) xs[lds_word(e)] = (hb + e >= 0) ? hist[hb + e] : 0.0f;
+    bool bad = false;
+    for (int e = tid; e < e_in0; e += PV_VARI_THREADS) {
+        const float v = (hb + e >= 0) ? hist[hb + e] : 0.0f;
+        xs[lds_word(e)] = v;
+        bad |= non_finite(v);
+    }
     for (int e = e_in1 + tid; e < span; e += PV_VARI_THREADS) xs[lds_word(e)] = 0.0f;
     {
         const int mis = (int)((((uintptr_t)in_c >> 2) + (uintptr_t)(long)(r0 + e_in0)) & 3);      // in_c + r0 + e_in0 - mis is 16-byte aligned
@@ -70,12 +122,18 @@ __global__ __launch_bounds__(PV_VARI_THREADS) void pv_vari_kernel(PvVariParams p
             if (e >= e_in0 && e + 4 <= e_in1) {
                 const float4 v = *(const float4 *)(in_c + (r0 + e));
                 xs[lds_word(e)] = v.x; xs[lds_word(e + 1)] = v.y; xs[lds_word(e + 2)] = v.z; xs[lds_word(e + 3)] = v.w;
+                bad = bad || non_finite(v.x) || non_finite(v.y) || non_finite(v.z) || non_finite(v.w);
             } else {
                 for (int u = 0; u < 4; u++)
-                    if (e + u >= e_in0 && e + u < e_in1) xs[lds_word(e + u)] = in_c[r0 + e + u];
+                    if (e + u >= e_in0 && e + u < e_in1) {
+                        const float v = in_c[r0 + e + u];
+                        xs[lds_word(e + u)] = v;
+                        bad |= non_finite(v);
+                    }
             }
         }
     }
+    if (bad) s_bad = 1;                                         // every writer stores the same value
     {
         const float4 *g4 = (const float4 *)p.table;
         for (int k = tid; k < PV_VARI_TABLE_WORDS / 4; k += PV_VARI_THREADS) ((float4 *)P)[k] = g4[k];
@@ -112,34 +170,9 @@ __global__ __launch_bounds__(PV_VARI_THREADS) void pv_vari_kernel(PvVariParams p
         rem[k] = (int)(aq - (unsigned)q[k] * (unsigned)den[k]);
         num[k] = 0.0f; sum[k] = 0.0f;
     }
-    // taps at or before the output position: a falls by c per tap
-    for (int i = i_lo; i < W; i++) {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-            const float w = weight(P, q[k], rem[k], inv[k]);
-            num[k] = fmaf(w, xs[lds_word(off[k] + i)], num[k]);
-            sum[k] += w;
-            q[k] -= dq[k]; rem[k] -= dr[k];
-            if (rem[k] < 0) { rem[k] += den[k]; q[k] -= 1; }
-        }
-    }
-    // (q, rem) now stands for a Q = (r - c) Q < 0, floored; tap W has a = c - r
-#pragma unroll
-    for (int k = 0; k < R; k++) {
-        q[k] = rem[k] == 0 ? -q[k] : -q[k] - 1;
-        rem[k] = rem[k] == 0 ? 0 : den[k] - rem[k];
-    }
-    // taps behind the output position: a grows by c per tap
-    for (int i = W; i <= i_hi; i++) {
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-            const float w = weight(P, q[k], rem[k], inv[k]);
-            num[k] = fmaf(w, xs[lds_word(off[k] + i)], num[k]);
-            sum[k] += w;
-            q[k] += dq[k]; rem[k] += dr[k];
-            if (rem[k] >= den[k]) { rem[k] -= den[k]; q[k] += 1; }
-        }
-    }
+    // workgroup-uniform: the select on the weight only where the span holds a sample it matters for
+    if (__builtin_amdgcn_readfirstlane(s_bad)) run_taps<R, true>(P, xs, i_lo, W, i_hi, off, inv, den, dq, dr, q, rem, num, sum);
+    else run_taps<R, false>(P, xs, i_lo, W, i_hi, off, inv, den, dq, dr, q, rem, num, sum);
     float *out = p.out + (long)ch * p.out_stride + j0;
 #pragma unroll
     for (int k = 0; k < R; k++) {

@@ -165,3 +165,85 @@ def test_stretch_then_variable_resampler_fits_the_closed_form(name):
     amp_gate, res_gate = (2 * v for v in GLIDE_MEASURED[name])
     print(f"glide {name}: amplitude ratio {ratio}, residual {res:.3e} (gates {amp_gate:.1e}, {res_gate:.1e})")
     assert np.max(np.abs(ratio - 1.0)) <= amp_gate and res <= res_gate, (name, ratio, res)
+
+
+# ---- non-finite input: the reach of a bad sample (pv_vari.h, NON-FINITE INPUT) ----
+
+def _reach_case():
+    """A small schedule whose counts lie on both sides of B (widened and plain taps), two calls, bad samples in the first T - 1 samples, mid-stream and
+    on the last sample of the first call."""
+    B, lo, hi = 20, 12, 40
+    rng = np.random.default_rng(20)
+    counts = np.array([12, 40, 12, 33, 20, 40, 13, 21, 40, 12], np.int64)
+    x = rng.standard_normal((3, counts.size * B)).astype(np.float32)
+    x[1, 5], x[1, 4 * B - 1], x[1, 7 * B] = np.nan, np.inf, -np.inf
+    x[2, 3 * B] = np.nan
+    return B, lo, hi, counts, x, 4
+
+
+def test_the_poisoned_mask_equals_a_per_output_evaluation_in_exact_arithmetic():
+    """Output by output and tap by tap in Python integers and f32 scalars, the weight's zero test in exact rationals: nothing shared with
+    VariModel.process but the definition."""
+    from fractions import Fraction
+    B, lo, hi, counts, x, cut = _reach_case()
+    m = VM.VariModel(B, lo, hi, 3)
+    W, T = m.W, m.T
+    P = VM.prototype()
+    ya, pa, na = m.process(x[:, :cut * B], counts[:cut], reach=True)
+    yb, pb, nb = m.process(x[:, cut * B:], counts[cut:], reach=True)
+    y, poisoned, near = np.concatenate([ya, yb], axis=1), np.concatenate([pa, pb], axis=1), np.concatenate([na, nb], axis=1)
+    stream = np.concatenate([np.zeros((3, T - 1), np.float32), x], axis=1)       # stream[:, T - 1 + e] = x[:, e], zeros before the stream
+    bad = ~np.isfinite(stream)
+    want_p, want_n = np.zeros_like(poisoned), np.zeros_like(near)
+    j = 0
+    for b, c in enumerate(counts.tolist()):
+        den = max(B, c)
+        inv = np.float32(1.0) / np.float32(den)
+        for k in range(c):
+            n, r = b * B + (k * B) // c, (k * B) % c
+            for i in range(T):
+                aq = abs((i - W + 1) * c - r) * VM.Q
+                q = min(aq // den, VM.HALF_WIDTH * VM.Q)
+                f, d = np.float32(aq % den) * inv, P[q + 1] - P[q]
+                assert type(f) is np.float32 and type(d) is np.float32
+                nonzero = Fraction(float(f)) * Fraction(float(d)) + Fraction(float(P[q])) != 0
+                hit = bad[:, n + i]                                                # tap i reads x[n - 2 W + 1 + i] = stream[n + i]
+                want_n[:, j] |= hit
+                if nonzero:
+                    want_p[:, j] |= hit
+            j += 1
+    assert j == counts.sum()
+    assert np.array_equal(poisoned, want_p) and np.array_equal(near, want_n)
+    assert not poisoned[0].any() and poisoned[1].any() and poisoned[2].any()
+    assert np.any(near & ~poisoned)                                                # some output has a bad sample under zero weights only
+    assert np.all(np.isfinite(y))
+    # the values are those of the stream with the bad samples replaced by 0, the history is the input as it came
+    z = VM.VariModel(B, lo, hi, 3)
+    assert np.array_equal(y, z.process(np.where(np.isfinite(x), x, np.float32(0.0)), counts))
+    assert np.array_equal(m.hist.view(np.uint32), x[:, x.shape[1] - (T - 1):].view(np.uint32))
+
+
+def test_a_clean_input_has_an_empty_mask_and_unchanged_results():
+    B, lo, hi, counts, x, cut = _reach_case()
+    x = np.where(np.isfinite(x), x, np.float32(0.25))
+    a, b = VM.VariModel(B, lo, hi, 3), VM.VariModel(B, lo, hi, 3)
+    plain = a.process(x, counts, bound=True)
+    with_reach = b.process(x, counts, bound=True, reach=True)
+    assert len(with_reach) == len(plain) + 2
+    for u, v in zip(plain, with_reach):
+        assert np.array_equal(u, v)
+    assert not with_reach[-2].any() and not with_reach[-1].any()
+    assert np.array_equal(a.hist, b.hist) and (a.blocks, a.outputs) == (b.blocks, b.outputs)
+    y2, p2, n2 = VM.VariModel(B, lo, hi, 3).process(x, counts, reach=True)
+    assert np.array_equal(y2, plain[0]) and not p2.any() and not n2.any()
+
+
+def test_the_kernel_weight_is_zero_exactly_from_32_widened_samples_on():
+    """On the shapes the GPU tests use no weight cancels to zero inside the prototype's support, so there `non-zero weight` is `closer than 32 max(1, B / c)
+    samples`; the mask does not rely on it."""
+    P = VM.prototype()
+    for B, c, W in [(320, 200, 52), (320, 440, 52), (64, 8, 256), (64, 512, 256), (64, 9, 256), (64, 511, 256)]:
+        r = (np.arange(c) * B) % c
+        nz = VM.nonzero_weights(B, c, r, W, P)
+        a = np.abs((np.arange(2 * W)[None, :] - W + 1) * c - r[:, None])
+        assert np.array_equal(nz, a * VM.Q // max(B, c) < VM.HALF_WIDTH * VM.Q)

@@ -66,6 +66,24 @@ def weights(B, c, r, W, table, exact=False):
     return P[qc] + f * d, np.abs(f * d)
 
 
+def nonzero_weights(B, c, r, W, table):
+    """bool[len(r), T]: the taps whose weight is non-zero IN THE KERNEL'S ARITHMETIC, w = fmaf(f32(rem) * (1.0f / f32(den)), P[q + 1] - P[q], P[q]).  The
+    product and the sum are evaluated in fp64 from the f32 operands f^ = fl(rem * fl(1 / den)) and d^ = fl(P[q + 1] - P[q]): f^ d^ is exact in fp64
+    (24 + 24 bits), and an exact f^ d^ + P[q] that is not zero is a multiple of 2^-298 no smaller than that, far inside the fp64 range, so the rounded
+    fp64 sum is zero exactly when the fused f32 operation gives zero.  (The model's own fp64 f = rem / den would answer another question.)"""
+    T = 2 * W
+    i = np.arange(T, dtype=np.int64)[None, :]
+    a = np.abs((i - W + 1) * int(c) - np.asarray(r, np.int64)[:, None])
+    den = max(int(B), int(c))
+    aq = a * Q
+    q = np.minimum(aq // den, HALF_WIDTH * Q)
+    P = np.asarray(table).astype(np.float32)
+    f = (aq % den).astype(np.float32) * (np.float32(1.0) / np.float32(den))
+    d = P[q + 1] - P[q]
+    assert f.dtype == np.float32 and d.dtype == np.float32
+    return f.astype(np.float64) * d.astype(np.float64) + P[q].astype(np.float64) != 0.0
+
+
 class VariModel:
     """One pv_vari handle with `nch` channel slots.  `table`: another f32[8194] in place of the model's own (the GPU tests pass the library's)."""
 
@@ -79,10 +97,15 @@ class VariModel:
         self.blocks = 0
         self.outputs = 0
 
-    def process(self, x, counts, bound=False, exact=False):
+    def process(self, x, counts, bound=False, exact=False, reach=False):
         """x: float32[nch, nblocks B], counts int[nblocks] -> fp64[nch, sum(counts)].  bound=True: also, per output sample, A = sum_i m_i |x_i|,
         S = sum_i m_i with m_i = |w_i| + |f_i (P[q_i + 1] - P[q_i])| >= |w_i|, D = sum_i w_i (one row: the weights are the same in every channel) and
-        Tloc, the number of non-zero weights."""
+        Tloc, the number of non-zero weights.
+        reach=True: the rule for non-finite input (pv_vari.h).  Every sample that is not finite, in the carried history or in x, counts as 0 in y (and
+        in A), and two bool[nch, total] are appended to the result: `poisoned`, the outputs with such a sample under a tap whose weight is non-zero
+        in the kernel's own arithmetic (nonzero_weights) -- the kernel gives a non-finite value exactly there -- and `near`, the outputs with such a
+        sample anywhere under their T taps.  The history keeps the samples as they came.  Without reach a non-finite sample poisons whatever fp64
+        makes of it (0 * nan): that is no statement about the kernel."""
         x = np.asarray(x, np.float32)
         if x.ndim == 1:
             x = x[None, :]
@@ -90,11 +113,14 @@ class VariModel:
         nch, nin = x.shape
         B, W, T = self.B, self.W, self.T
         assert nin == counts.size * B and np.all((counts >= self.min_count) & (counts <= self.max_count))
-        buf = np.concatenate([self.hist[:nch], x], axis=1).astype(np.float64)          # buf[:, e] = call-relative input index e - (T - 1)
+        raw = np.concatenate([self.hist[:nch], x], axis=1)                             # raw[:, e] = call-relative input index e - (T - 1)
+        bad = ~np.isfinite(raw) if reach else None
+        buf = (np.where(bad, np.float32(0.0), raw) if reach else raw).astype(np.float64)
         total = int(counts.sum())
         y = np.zeros((nch, total), np.float64)
         A = np.zeros((nch, total), np.float64)
         S, D, Tloc = np.zeros(total, np.float64), np.zeros(total, np.float64), np.zeros(total, np.int64)
+        poisoned, near = np.zeros((nch, total), bool), np.zeros((nch, total), bool)
         at = 0
         for b, c in enumerate(counts.tolist()):
             k = np.arange(c, dtype=np.int64)
@@ -109,16 +135,23 @@ class VariModel:
                 D[sl] = w.sum(axis=1)
                 S[sl] = m.sum(axis=1)
                 Tloc[sl] = (w != 0.0).sum(axis=1)
+                nz = nonzero_weights(B, c, r[s:s + step], W, self.table) if reach else None
                 for ch in range(nch):
                     xv = buf[ch][idx]
                     y[ch, sl] = (w * xv).sum(axis=1) / D[sl]
                     if bound:
                         A[ch, sl] = (m * np.abs(xv)).sum(axis=1)
+                    if reach and bad[ch].any():
+                        poisoned[ch, sl] = (nz & bad[ch][idx]).any(axis=1)
+                        near[ch, sl] = bad[ch][idx].any(axis=1)
             at += c
-        self.hist[:nch] = buf[:, buf.shape[1] - (T - 1):].astype(np.float32)
+        self.hist[:nch] = raw[:, raw.shape[1] - (T - 1):]
         self.blocks += counts.size
         self.outputs += total
-        return (y, A, S, D, Tloc) if bound else y
+        res = (y, A, S, D, Tloc) if bound else (y,)
+        if reach:
+            res += (poisoned, near)
+        return res if len(res) > 1 else y
 
 
 def positions(block, counts, W):

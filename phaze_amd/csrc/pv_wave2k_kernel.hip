@@ -31,6 +31,10 @@
 #define PV_PT 1, 0, 1, 2, 3, 2, 3, 3, 0, 0, 0, 2     // phase priorities of this kernel (pv_wave_fft.h; profiles/r03_priority_sweep.md: C3 3.76 -> 3.31 ms; re-swept in round 5 on the
                                                      // fp32-first kernel: split arithmetic, scatter and c2r pass at level 3 -- C3 3.024 -> 2.991 ms, 2048/128 at f = 0.8 3.189 -> 3.141)
 #endif
+#ifndef PV_TW_EARLY
+#define PV_TW_EARLY 0                                // no room here: this kernel runs at 256 registers, and the twiddle reads in front of the radix-8 cost six of its
+                                                     // instances spilled registers (tools/experiments/README.md)
+#endif
 #include "pv_wave_fft.h"
 #include "pv_guard.h"
 #ifdef PV_W2K_STAMPS  // measurement build (make variant ... EXTRA=-DPV_W2K_STAMPS CAPI_EXTRA=-DPV_STAMPS=1): s_memtime at the stations of a 1-hop launch, per chain

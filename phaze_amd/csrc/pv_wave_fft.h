@@ -134,17 +134,51 @@ __device__ __forceinline__ void fft512_wave(typename v2t<T>::type (&a)[8], typen
 // are padded to TPP = 72 slots (1152 B = 128 mod 256): the four rows a read touches fall on alternating halves of the 64 banks -> 2 passes,
 // the minimum for 512 bytes (checked with tools/lds_layout_check.py pairs).
 constexpr int TPP = 72;
+
+// ---- LDS reads issued ahead of the work that hides them ----
+// A table read whose address depends on the lane id alone can be issued long before its use, but the scheduler, short of registers, puts it next to the use: the
+// wave then sits in s_waitcnt lgkmcnt for the whole round trip (11 % of a wave's life in the N = 1024 frame).  lds_read_here() is a volatile address-space-3 load,
+// lds_reads_issued() a scheduling barrier behind a batch of them: the reads stand in the ISA where they stand in the source, the arithmetic that follows runs while
+// they travel, and the first use waits for what is left.  No value is computed differently.  tools/lds_wait_points.py lists every wait of a frame loop.
+template <typename V> __device__ __forceinline__ V lds_read_here(const V *p) { return *(const volatile __attribute__((address_space(3))) V *)p; }
+__device__ __forceinline__ void lds_reads_issued() { __builtin_amdgcn_sched_barrier(0); }
+// PV_TW_EARLY: which uses of fft512_wave_inv_pk issue the four twiddle reads of a pass in front of that pass's radix-8 (bit 0: the fp32 forward transform, bit 1: the
+// inverse).  The reads hold 16 registers across the 26 instructions of the radix-8; a kernel file without that room defines its own value before including this header.
+#ifndef PV_TW_EARLY
+#define PV_TW_EARLY 3
+#endif
+// One pass of the packed inverse FFT with its twiddle reads in front: tw[j * STRIDE + i] holds the twiddles of outputs 2 j and 2 j + 1.  Output 0 has none: of row 0
+// only the upper half is read (the dead half's registers would be reused at once, and their next writer would wait for the read to land).
+template <int STRIDE>
+__device__ __forceinline__ void radix8_inv_twiddles_first(pk::c32 (&a)[8], const v4f *tw, int i)
+{
+    const pk::c32 t1 = lds_read_here(reinterpret_cast<const pk::c32 *>(&tw[i]) + 1);
+    v4f t[4];
+#pragma unroll
+    for (int j = 1; j < 4; j++) t[j] = lds_read_here(&tw[j * STRIDE + i]);
+    lds_reads_issued();
+    pk::radix8_inv(a);
+    a[1] = pk::cmul(a[1], t1);
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        a[2 * j] = pk::cmul(a[2 * j], pk::c32{t[j].x, t[j].y});
+        a[2 * j + 1] = pk::cmul(a[2 * j + 1], pk::c32{t[j].z, t[j].w});
+    }
+}
 // REGT1 = false keeps transpose 1 in LDS: needed when `l` is NOT the physical lane id (pv_wave2k_kernel relabels the lanes of odd frames at hop 128).
 // FWDPH = true: the instance that serves as the fp32 FORWARD transform (round 5: FFT(z) = conj(IFFT(conj z)), the conjugations folded into the window product
 // and the split pass) -- same arithmetic, the forward phases' priorities.
+// st(3) stands in front of pass 3, behind the last transpose read: the caller of the inverse instance issues the reads of its window rows there, and the 26 packed
+// instructions of the pass hide them (the forward instance passes nothing and pays nothing).
 template <bool REGT1 = true, typename ST = NoStamp, bool FWDPH = false>
 __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, const v4f *TW1F4, const v4f *TW2F4, int l, ST st = ST{})
 {
     constexpr int PHX = FWDPH ? PH_FX : PH_IX, PHA = FWDPH ? PH_FA : PH_IA, PHP3 = FWDPH ? PH_FP3 : PH_IP3;
-    constexpr bool MATH = !(PV_ABL & 4), XPOSE = !(PV_ABL & 8);
+    constexpr bool MATH = !(PV_ABL & 4), XPOSE = !(PV_ABL & 8), TWE = (PV_TW_EARLY & (FWDPH ? 1 : 2)) != 0;
     const int lh = l >> 3, ll = l & 7;
     v4f *S4 = reinterpret_cast<v4f *>(S);
-    if (MATH) {
+    if (MATH && TWE) radix8_inv_twiddles_first<64>(a, TW1F4, l);
+    else if (MATH) {
         pk::radix8_inv(a);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -173,7 +207,8 @@ __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, 
         pv_prio(PHA);
     }
     st(1);
-    if (MATH) {
+    if (MATH && TWE) radix8_inv_twiddles_first<8>(a, TW2F4, ll);
+    else if (MATH) {
         pk::radix8_inv(a);
 #pragma unroll
         for (int j = 0; j < 4; j++) {

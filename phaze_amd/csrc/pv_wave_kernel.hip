@@ -1157,6 +1157,10 @@ resident_top:
         int upper_end = H;
         if (last_peak >= 0 && last_shift < 0) { upper_end = H - last_shift; if (upper_end > N) upper_end = N; }      // DROP is positive
         pk::c32 zi[8];
+        // the window rows of the overlap-add are read inside the packed inverse transform (not in the tap instance, where they cost a spilled register, and not in the
+        // fp64 flavour, whose fp64 inverse transform has no place for them)
+        constexpr bool HANN_EARLY = !AUX && !(SPREAD && FP64);
+        v4f hq[4];
         if constexpr (SPREAD && FP64) {
             // ---- fp64 flavour: shift, c2r pass and inverse FFT in doubles (see PV_FP64_FLAVOUR at the top) ----
             wave_sync();
@@ -1239,11 +1243,21 @@ resident_top:
         // ---- zero Y (pv:121).  The magnitudes have been read (LDS instructions of a wave execute in order): the routes (SPREAD) / Y's tail (!SPREAD) may overwrite them ----
         wave_sync();
         float2 *Yn = reinterpret_cast<float2 *>(smem + OFF_Y);               // SPREAD: Y as a plain array of 513 bins
+        // SPREAD: the nine routes of a lane (source bins l + 64 r, 512 - l - 64 r and 256), read in one batch -- see the scatter below
+        [[maybe_unused]] unsigned ra[4], rb[4], r256;
+        [[maybe_unused]] auto read_routes = [&]() {
+            const unsigned *ROUTE = reinterpret_cast<const unsigned *>(smem + OFF_ROUTE);
+#pragma unroll
+            for (int r = 0; r < 4; r++) { ra[r] = lds_read_here(&ROUTE[l + 64 * r]); rb[r] = lds_read_here(&ROUTE[512 - l - 64 * r]); }
+            r256 = lds_read_here(&ROUTE[256]);                              // every lane reads the one word: a broadcast
+        };
         if constexpr (SPREAD) {
             unsigned *ROUTE = reinterpret_cast<unsigned *>(smem + OFF_ROUTE);
             *reinterpret_cast<uint4 *>(&ROUTE[8 * l]) = uint4{rt[0], rt[1], rt[2], rt[3]};
             *reinterpret_cast<uint4 *>(&ROUTE[8 * l + 4]) = uint4{rt[4], rt[5], rt[6], rt[7]};
             if (l == 63) ROUTE[512] = rt512;
+            wave_sync();                                                    // the table is published here, and the zeroing stores queue behind the route reads
+            read_routes();                                                  // (behind them the batch waited for four ds_write_b128: +0.5 %, profiles/lds_hoists_ab.md)
 #pragma unroll
             for (int r = 0; r < 4; r++) *reinterpret_cast<v4f *>(&Yn[2 * l + 128 * r]) = v4f{0.f, 0.f, 0.f, 0.f};     // 16 bytes per lane and store
             if (l == 0) Yn[512] = float2{0.f, 0.f};
@@ -1272,16 +1286,19 @@ resident_top:
             if constexpr (SPREAD) {
                 // delta_i = round(p_i f) - p_i is non-decreasing in i for f >= 1, the shifted regions stay disjoint: plain stores of the register-resident
                 // source bins along the routes of the table
-                const unsigned *ROUTE = reinterpret_cast<const unsigned *>(smem + OFF_ROUTE);
+                // All nine routes of a lane are read in ONE batch (read_routes above: directly behind the barrier that publishes the table, in front of the zeroing) and waited for once HERE.  Read next to their
+                // stores they were five dependent LDS round trips at priority 3: the table and Y are both pointers into the wave's block, and the compiler may not
+                // move a read of one above a store to the other (they cannot overlap: Y ends at byte 4104, the table starts at OFF_ROUTE = 4352).  Bin 256 is read
+                // by every lane (one address: a broadcast) and stored by lane 0 under its predicate -- no scalar branch around a read of its own.
+                asm volatile("" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]), "+v"(r256));   // the one wait
                 auto scatter = [&](auto mode_tag) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        const unsigned ra = ROUTE[l + 64 * r], ta = ra & 0xFFFFu;
-                        const unsigned rb = ROUTE[512 - l - 64 * r], tb = rb & 0xFFFFu;
-                        if (ta < (unsigned)H) Yn[ta] = rot_mode(mode_tag, ra, XA[r]);
-                        if (tb < (unsigned)H) Yn[tb] = rot_mode(mode_tag, rb, XB[r]);
+                        const unsigned ta = ra[r] & 0xFFFFu, tb = rb[r] & 0xFFFFu;
+                        if (ta < (unsigned)H) Yn[ta] = rot_mode(mode_tag, ra[r], XA[r]);
+                        if (tb < (unsigned)H) Yn[tb] = rot_mode(mode_tag, rb[r], XB[r]);
                     }
-                    if (l == 0) { const unsigned r256 = ROUTE[256], tg = r256 & 0xFFFFu; if (tg < (unsigned)H) Yn[tg] = rot_mode(mode_tag, r256, x256f); }
+                    { const unsigned tg = r256 & 0xFFFFu; if (l == 0 && tg < (unsigned)H) Yn[tg] = rot_mode(mode_tag, r256, x256f); }
                 };
                 if (tmod == 0) scatter(std::integral_constant<int, 0>{});
                 else if (tmod == N / 2) scatter(std::integral_constant<int, 2>{});
@@ -1390,11 +1407,20 @@ resident_top:
             }
         }
         wave_sync();
+        // the 0.5 * Hann rows of the window product below are read in front of pass 3 (their address is the lane id's alone): issued behind the pass, the product waited a
+        // whole LDS round trip for them
+        auto hann_rows = [&](int id) {
+            if (id != 3 || !HANN_EARLY) return;
+#pragma unroll
+            for (int j = 0; j < 4; j++) hq[j] = lds_read_here(&HW4[j * 64 + l]);
+            lds_reads_issued();
+        };
 #ifdef PV_STAMPS
         stamps.mark(7);
-        fft512_wave_inv_pk<true>(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, [&](int id) { if (id & 1) stamps.mark(8 + id); else stamps.mark(8 + id, true); });
+        fft512_wave_inv_pk<true>(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, [&](int id) { hann_rows(id); if (id & 1) stamps.mark(8 + id); else stamps.mark(8 + id, true); });
 #else
-        fft512_wave_inv_pk(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l);
+        if constexpr (HANN_EARLY) fft512_wave_inv_pk(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, hann_rows);
+        else fft512_wave_inv_pk(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l);
 #endif
         }
         // The rows and the pitchFactor prefetched for the next frame are CONSUMED here, in front of this frame's output stores.  vmcnt counts loads and stores in ONE queue, in
@@ -1412,7 +1438,10 @@ resident_top:
             const bool emit_out = (m >= emit_v);
             float2 fr[8];
 #pragma unroll
-            for (int j = 0; j < 4; j++) { const v4f h = HW4[j * 64 + l]; hw[2 * j] = pk::c32{h.x, h.y}; hw[2 * j + 1] = pk::c32{h.z, h.w}; }   // stays live for the next frame
+            for (int j = 0; j < 4; j++) {
+                if constexpr (!HANN_EARLY) hq[j] = HW4[j * 64 + l];
+                hw[2 * j] = pk::c32{hq[j].x, hq[j].y}; hw[2 * j + 1] = pk::c32{hq[j].z, hq[j].w};   // stays live for the next frame
+            }
 #pragma unroll
             for (int r = 0; r < 8; r++) { const pk::c32 f = pk::mul(zi[r], hw[r]); fr[r] = float2{f.x, f.y}; }   // the windowed frame is ROUNDED to fp32 before it is accumulated
                                                                                                                // (Float32Array, pv:67): an asm multiply -- a plain one is contracted into the adds below (v_pk_fma_f32), one rounding less than the reference

@@ -94,8 +94,10 @@ def js_round(x):
     return np.where(x - r >= 0.5, r + 1.0, r)
 
 
-def shift_spectrum(Xlow, res_upper, pitch_f32, t, N):
-    """findPeaks + shiftPeaks as per-bin parallel rules.  Xlow: complex128[N/2+1]; res_upper: complex[N] or None."""
+def shift_spectrum(Xlow, res_upper, pitch_f32, t, N, contributions=False):
+    """findPeaks + shiftPeaks as per-bin parallel rules.  Xlow: complex128[N/2+1]; res_upper: complex[N] or None.
+    contributions=True appends a second result, (A, n, n_res), each [N/2+1]: for every target bin k the sum A[k] of |X[src]| (float64) over the source bins that
+    land on k, their number n[k], and how many of them lie above Nyquist (the residue) -- what tests/level_model.spectrum_bound scales its per-bin bound with."""
     H = N // 2 + 1
     mag = (Xlow.real * Xlow.real + Xlow.imag * Xlow.imag).astype(np.float32)
     k = np.arange(H)
@@ -104,6 +106,8 @@ def shift_spectrum(Xlow, res_upper, pitch_f32, t, N):
     flag[2:H - 2] = (mag[kk] > mag[kk - 1]) & (mag[kk] > mag[kk - 2]) & (mag[kk] > mag[kk + 1]) & (mag[kk] > mag[kk + 2])
     Y = np.zeros(H, dtype=np.complex64)
     if not flag.any():
+        if contributions:
+            return Y, mag, np.nonzero(flag)[0], (np.zeros(H), np.zeros(H, np.int64), np.zeros(H, np.int64))
         return Y, mag, np.nonzero(flag)[0]
     # nearest peak at or below / strictly above each source bin b in [0, N)
     b = np.arange(N)
@@ -132,6 +136,16 @@ def shift_spectrum(Xlow, res_upper, pitch_f32, t, N):
     ridx = (d % N) * (int(t) % N) % N
     rot = np.exp(2j * np.pi * ridx / N)
     np.add.at(Y, tgt[ok].astype(np.int64), (src[ok] * rot).astype(np.complex64))
+    if contributions:
+        amp = np.concatenate([np.abs(np.asarray(Xlow, np.complex128)), np.zeros(N - H)])
+        if res_upper is not None:
+            amp[H:] = np.abs(np.asarray(res_upper[H:], np.complex128))
+        A, n, n_res = np.zeros(H), np.zeros(H, np.int64), np.zeros(H, np.int64)
+        ti = tgt[ok].astype(np.int64)
+        np.add.at(A, ti, amp[ok])
+        np.add.at(n, ti, 1)
+        np.add.at(n_res, ti, (b[ok] >= H).astype(np.int64))
+        return Y, mag, np.nonzero(flag)[0], (A, n, n_res)
     return Y, mag, np.nonzero(flag)[0]
 
 

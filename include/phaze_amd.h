@@ -54,7 +54,7 @@ typedef struct pv_handle pv_handle;
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
- *     pv_tune_plan. */
+ *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -662,6 +662,85 @@ typedef struct pv_tune_params {
 /* Returns the number of frames planned and writes at most `capacity` of them (the two-call sizing of pv_transient_plan): hops[m], and when curve is
  * not NULL the shift r of frame m in octaves.  records: nrec records of one channel, contiguous.  -PV_ERR_ARGUMENT for an argument out of range. */
 PV_API int64_t pv_tune_plan(const pv_tune_params *p, const int32_t *records, int64_t nrec, int32_t *hops, double *curve, int64_t capacity);
+
+/* ---- formant-preserving pitch correction: pitch-synchronous overlap-add (TD-PSOLA) on a grain table ------------------------------------ */
+/* For a monophonic voice.  Two-period Hann grains are cut at the pitch period, re-spaced at period / ratio and overlap-added: a grain keeps the
+ * vocal tract's response, so the spectral envelope stays where it was and only the spacing, the pitch, moves; duration is kept by construction.
+ * The marks are spaced at the period but NOT aligned to the glottal epochs (DESIGN.md "Pitch-synchronous correction" has the measured cost), and
+ * one grain table serves every channel of a call, so a stereo pair keeps its image.
+ * A grain is four int32 {t, tf, dq, L}: a Hann window of half length L samples centred at output position t + tf / 256 (tf in 0 .. 255) over the
+ * input shifted by dq / 256 samples, i.e. output n of the grain reads the input at the real position n - dq / 256.  2 <= L <= max_period <= 4096,
+ * |dq| <= 256 max_period, centres non-decreasing, positions relative to the buffer and below 2^30.  For output n and grain g:
+ *   window   ua = |256 (n - t) - tf|; the weight is 0 when ua >= 256 L, else q = (4 ua) div L, rem = (4 ua) mod L, f = f32(rem) * (1.0f / f32(L)) and
+ *            h = fmaf(f, Hn[q + 1] - Hn[q], Hn[q]) with the table Hn of pv_psola_window.
+ *   sample   D = dq div 256, phi = dq mod 256 (floored).  phi == 0: the sample x[n - D] itself, so an unshifted grain is transparent.  Else
+ *            theta = 256 - phi, b = n - D - 1 and 64 taps i = 0 .. 63 read x[b - 31 + i] with weight w_i = P[|256 (i - 31) - theta|], P the table of
+ *            pv_vari_prototype used without interpolation: a = fmaf(w_i, x_i, a) and s = s + w_i for i ascending, xt = a / s.  x is 0 outside [0, nin).
+ *   output   for the grains g ascending with h != 0: num = fmaf(h, xt, num), den = den + h; y[n] = num / den, or 0 where no grain covers n.
+ * The order of every sum is a function of (g, i) alone: outputs [out_first, out_first + nout) are a pure function of (buffer, grains), and any
+ * partition of the range into calls gives the same bits.  y[n] is non-finite exactly when a non-finite sample lies under a tap of a grain with
+ * h != 0 (all 64 taps, or the one sample when phi == 0). */
+typedef struct pv_psola_config {
+    int32_t struct_size;     /* sizeof(pv_psola_config) as the caller compiled it (PV_PSOLA_CONFIG_INIT sets it)                  */
+    int32_t max_period;      /* the largest half length L and the largest |dq| / 256 a call may pass, 2 .. 4096                  */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_psola_config;
+#define PV_PSOLA_CONFIG_INIT { (int32_t)sizeof(pv_psola_config), 0, 0, 0, 0, 0 }
+
+typedef struct pv_psola pv_psola;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_psola_last_error(NULL). */
+PV_API int pv_psola_create(const pv_psola_config *cfg, pv_psola **out);
+PV_API int pv_psola_destroy(pv_psola *h);
+PV_API const char *pv_psola_last_error(const pv_psola *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_psola_set_stream(pv_psola *h, void *hip_stream);
+PV_API int pv_psola_synchronize(pv_psola *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1: channel c reads in[c*in_stride .. + nin) and writes out[c*out_stride .. + nout),
+ * out[0] being output out_first.  grains: ngrains records of four int32 on the HOST, one table for all channels.  Stateless.  Rejected with
+ * PV_ERR_ARGUMENT before any device work and with the output untouched: a null buffer, a negative count, a position of 2^30 or more, with nch > 1
+ * strides below nin / nout, and a grain out of range or out of order (the message names the grain).  nch > max_channels: PV_ERR_CAPACITY.  Host
+ * pointers, synchronous, staged in pieces of max_outputs. */
+PV_API int pv_psola_process(pv_psola *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains, float *out,
+                            int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains stay a host table), asynchronous on the handle's stream. */
+PV_API int pv_psola_process_device(pv_psola *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains,
+                                   float *d_out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* Pure host code, no handle and no device: the window table Hn, 1026 floats, Hn[q] = f32((1 + cos(pi q / 1024)) / 2) for q < 1024 and two zeros, with
+ * the two-call sizing of pv_vari_prototype. */
+PV_API int64_t pv_psola_window(float *table, int64_t capacity);
+
+/* One pitch ratio per f0 record, pure host code: the target rule of pv_tune_plan (scale_mask, strength, a4, sample_rate; the hop fields, input_len and
+ * shift are ignored) with the one-pole running per RECORD: r_j = r_(j-1) + retune (t_j - r_(j-1)), t_j = 0 for an unvoiced or empty record, and
+ * ratios[j] = 2^r_j held within [1/2, 2].  Returns nrec and writes at most `capacity` ratios; -PV_ERR_ARGUMENT for an argument out of range. */
+PV_API int64_t pv_psola_ratios(const pv_tune_params *p, const int32_t *records, int64_t nrec, double *ratios, int64_t capacity);
+
+/* The grain table that moves every voiced stretch by its ratio.  rec(x) = clamp((floor(x) - f0_center + f0_hop div 2) div f0_hop, 0, nrec - 1);
+ * P(x) is pv_f0_period of that record held within [min_period, max_period], unvoiced_period where it is 0 (and without records); rho(x) its ratio,
+ * 1 where it is unvoiced or ratios is NULL.  Analysis marks A_0 = 0, A_(i+1) = A_i + P(A_i); synthesis marks T_0 = 0,
+ * T_(k+1) = T_k + min(P(T_k) / rho(T_k), cap), cap = max(2 max_period - 4, 1), while T_k < input_len, all in fp64.  Grain k takes the analysis mark
+ * A_i nearest T_k (ties to the lower; a monotone walk).  Where both T_k and A_i fall on unvoiced records, A_i < input_len and
+ * 1 <= A_i - T_(k-1) <= cap, T_k becomes A_i: unvoiced material passes unshifted.  Then c = floor(256 T_k + 1/2), t = c div 256, tf = c mod 256,
+ * dq = floor(256 (T_k - A_i) + 1/2) and L = clamp(max(floor(P(A_i) + 1/2), floor(g / 2) + 2), 2, max_period), g the larger of the distances to the
+ * marks before and after T_k (after the last one: to where the next would be), so that neighbouring grains always overlap.  Centres are strictly
+ * ascending and |dq| <= 128 max_period + 256. */
+typedef struct pv_psola_params {
+    int32_t struct_size;     /* sizeof(pv_psola_params) as the caller compiled it (PV_PSOLA_PARAMS_INIT sets it)                  */
+    int32_t f0_hop;          /* the tracker's hop                                                                                */
+    int32_t f0_center;       /* where in its span a record is taken to sit, normally (W + max_lag) / 2                           */
+    int32_t min_period;      /* >= 2: shorter periods are held here                                                              */
+    int32_t max_period;      /* <= 4096: longer periods are held here; no half length exceeds it (the handle's max_period)       */
+    int32_t reserved;        /* must be 0                                                                                        */
+    double unvoiced_period;  /* the mark spacing where there is no pitch, within [min_period, max_period]                        */
+    int64_t input_len;       /* samples per channel of the input, below 2^30                                                     */
+} pv_psola_params;
+#define PV_PSOLA_PARAMS_INIT { (int32_t)sizeof(pv_psola_params), 0, 0, 0, 0, 0, 0.0, 0 }
+/* Returns the number of grains planned and writes at most `capacity` of them (four int32 each; the two-call sizing of pv_transient_plan).  records:
+ * nrec records of one channel; ratios: nrec values within [1/2, 2] or NULL.  -PV_ERR_ARGUMENT for an argument out of range. */
+PV_API int64_t pv_psola_plan(const pv_psola_params *p, const int32_t *records, int64_t nrec, const double *ratios, int32_t *grains, int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,8 @@ EXPORTS = [
     "pv_glide_process", "pv_glide_process_device", "pv_glide_stretch", "pv_glide_resampler",
     "pv_f0_create", "pv_f0_destroy", "pv_f0_last_error", "pv_f0_set_stream", "pv_f0_synchronize", "pv_f0_track", "pv_f0_track_device", "pv_f0_period",
     "pv_tune_plan",
+    "pv_psola_create", "pv_psola_destroy", "pv_psola_last_error", "pv_psola_set_stream", "pv_psola_synchronize", "pv_psola_process",
+    "pv_psola_process_device", "pv_psola_window", "pv_psola_ratios", "pv_psola_plan",
 ]
 
 
@@ -81,6 +83,25 @@ class _F0Config(C.Structure):
 class _TuneParams(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("struct_size", "f0_hop", "f0_center", "scale_mask", "synthesis_hop", "min_hop", "max_hop", "reserved")]
                 + [(n, C.c_double) for n in ("sample_rate", "a4", "strength", "retune")] + [(n, C.c_int64) for n in ("input_len", "shift")])
+
+
+class _PsolaConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+class _PsolaParams(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("struct_size", "f0_hop", "f0_center", "min_period", "max_period", "reserved")]
+                + [("unvoiced_period", C.c_double), ("input_len", C.c_int64)])
+
+
+def make_psola_config(max_period, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_psola_config with struct_size filled in (the C side's PV_PSOLA_CONFIG_INIT)."""
+    return _PsolaConfig(C.sizeof(_PsolaConfig), max_period, max_channels, max_outputs, device_id, flags)
+
+
+def make_psola_params(f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period):
+    """pv_psola_params with struct_size filled in (the C side's PV_PSOLA_PARAMS_INIT)."""
+    return _PsolaParams(C.sizeof(_PsolaParams), f0_hop, f0_center, min_period, max_period, 0, unvoiced_period, input_len)
 
 
 def make_f0_config(window, hop, min_lag, max_lag, max_channels=1, max_frames=0, device_id=0, flags=0):
@@ -272,6 +293,16 @@ def load_library():
     L.pv_f0_track_device.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64]
     L.pv_f0_period.argtypes = [ip]
     L.pv_tune_plan.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, ip, C.POINTER(C.c_double), C.c_int64]
+    L.pv_psola_create.argtypes = [C.POINTER(_PsolaConfig), C.POINTER(vp)]
+    L.pv_psola_destroy.argtypes = [vp]
+    L.pv_psola_last_error.argtypes = [vp]
+    L.pv_psola_set_stream.argtypes = [vp, vp]
+    L.pv_psola_synchronize.argtypes = [vp]
+    L.pv_psola_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_psola_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_psola_window.argtypes = [fp, C.c_int64]
+    L.pv_psola_ratios.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, C.POINTER(C.c_double), C.c_int64]
+    L.pv_psola_plan.argtypes = [C.POINTER(_PsolaParams), ip, C.c_int64, C.POINTER(C.c_double), ip, C.c_int64]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -286,6 +317,8 @@ def load_library():
     L.pv_f0_last_error.restype = C.c_char_p
     L.pv_f0_period.restype = C.c_double
     L.pv_tune_plan.restype = C.c_int64
+    L.pv_psola_last_error.restype = C.c_char_p
+    L.pv_psola_window.restype = L.pv_psola_ratios.restype = L.pv_psola_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1265,3 +1298,122 @@ class F0Tracker(_Handle):
     def track_device(self, d_in, nch, nframes, in_stride, d_records, rec_stride, threshold=2458):
         """pv_f0_track_device on raw device pointers (ints), asynchronous on the handle's stream; rec_stride counts records."""
         self._check(self._L.pv_f0_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, int(threshold), C.c_void_p(d_records), rec_stride))
+
+
+def psola_window():
+    """pv_psola_window: the window table Hn float32[1026] of the overlap-add kernel, Hn[q] = (1 + cos(pi q / 1024)) / 2 for q < 1024 and two zeros."""
+    L_ = load_library()
+    n = L_.pv_psola_window(None, 0)
+    table = np.zeros(n, np.float32)
+    L_.pv_psola_window(_fp(table), n)
+    return table
+
+
+def _one_channel_records(records):
+    r = np.ascontiguousarray(records, dtype=np.int32)
+    if r.size and (r.ndim != 2 or r.shape[1] != 4):
+        raise ValueError("records must be int32[nrec, 4]: one channel")
+    return r, (r.shape[0] if r.size else 0)
+
+
+def tune_ratios(records, sample_rate, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0):
+    """pv_psola_ratios: one pitch ratio (float64, within [1/2, 2]) per f0 record of ONE channel: the target rule of tune_plan with the one-pole running
+    per record; 1 where a record is unvoiced and the pole has settled."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    p = make_tune_params(0, 0, float(sample_rate), 0, 0, 0, 0, scale_mask, float(strength), float(retune), float(a4), 0)
+    out = np.zeros(nrec, np.float64)
+    n = L.pv_psola_ratios(C.byref(p), r.ctypes.data_as(C.POINTER(C.c_int32)) if nrec else None, nrec, out.ctypes.data_as(C.POINTER(C.c_double)) if nrec else None, nrec)
+    if n < 0:
+        raise ValueError("tune_ratios: bad argument (scale_mask 1 .. 0xFFF, strength 0 .. 1, retune (0, 1], positive rates)")
+    return out
+
+
+def psola_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None):
+    """pv_psola_plan: the grain table int32[ngrains, 4] = {t, tf, dq, L} of Psola.process that moves every voiced stretch of ONE channel's records by
+    its ratio (float64[nrec] within [1/2, 2]; None: 1 everywhere) and passes unvoiced stretches unshifted."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    rho = None
+    if ratios is not None:
+        rho = np.ascontiguousarray(ratios, dtype=np.float64)
+        if rho.shape != (nrec,):
+            raise ValueError("ratios must be float64[nrec]")
+    p = make_psola_params(int(f0_hop), int(f0_center), int(input_len), float(unvoiced_period), int(min_period), int(max_period))
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rp = r.ctypes.data_as(ip) if nrec else None
+    qp = rho.ctypes.data_as(dp) if rho is not None and nrec else None
+    n = L.pv_psola_plan(C.byref(p), rp, nrec, qp, None, 0)
+    if n < 0:
+        raise ValueError("psola_plan: bad argument (2 <= min_period <= unvoiced_period <= max_period <= 4096, ratios within [1/2, 2], 0 <= input_len < 2^30)")
+    grains = np.zeros((n, 4), np.int32)
+    if n:
+        L.pv_psola_plan(C.byref(p), rp, nrec, qp, grains.ctypes.data_as(ip), n)
+    return grains
+
+
+class Psola(_Handle):
+    """Pitch-synchronous overlap-add (pv_psola_*): formant-preserving pitch correction of a monophonic voice.  A grain int32[4] = {t, tf, dq, L} is a
+    Hann window of half length L centred at output position t + tf / 256 over the input shifted by dq / 256 samples; one table serves every channel.
+    Stateless: outputs [out_first, out_first + nout) are a pure function of (x, grains), and any partition of the range gives the same bits."""
+
+    _prefix = "pv_psola"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_psola_config(max_period, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_channels = max_period, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    @staticmethod
+    def _grains(grains):
+        g = np.ascontiguousarray(grains, dtype=np.int32)
+        if g.size and (g.ndim != 2 or g.shape[1] != 4):
+            raise ValueError("grains must be int32[ngrains, 4]")
+        return g, (g.shape[0] if g.size else 0)
+
+    def process(self, x, grains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), grains: int32[ngrains, 4] -> float32[nch, nout], outputs out_first .. out_first + nout - 1 (default: all n)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        g, ng = self._grains(grains)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_psola_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng, _fp(y), int(out_first), nout,
+                                             max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, grains, d_out, out_first, nout, out_stride):
+        """pv_psola_process_device on raw device pointers (ints), asynchronous on the handle's stream; grains is a host table."""
+        g, ng = self._grains(grains)
+        self._check(self._L.pv_psola_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng,
+                                                    C.c_void_p(d_out), out_first, nout, out_stride))
+
+    def process_tuned(self, x, sample_rate, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0):
+        """Offline formant-preserving pitch correction onto a scale: F0Tracker.track (channel 0: one plan for all channels) -> tune_ratios -> psola_plan
+        -> process.  x: float32[nch, n] (host).  tracker: an F0Tracker, default window 1024, hop 256, min_lag 32 and max_lag = max_period.  Returns
+        (y of the shape of x, grains)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        own = tracker is None
+        if own:
+            max_lag = max(self.max_period, 3)
+            tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
+        try:
+            records = tracker.track(x[0], threshold)[0]
+        finally:
+            if own:
+                tracker.close()
+        ratios = tune_ratios(records, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+        min_period = tracker.min_lag
+        grains = psola_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                            self.max_period, ratios)
+        y = self.process(x, grains)
+        return (y[0] if one else y), grains

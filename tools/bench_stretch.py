@@ -17,8 +17,10 @@ With --vari: the variable-ratio resampler (pv_vari_process_device) on the same s
 the same two hop rows, with its ratio to the stretch line.
 With --f0: only the f0 tracker (pv_f0_track_device) at W = 1024, max_lag = 1024, hop = 256, lags from 32, mono and 8 channels, --f0-frames frames per
 channel of a harmonic tone; frames/s counts channel-frames, and `macs_per_s` is frames/s times the W * max_lag multiply-adds of a frame's lag products.
+With --psola: only the pitch-synchronous overlap-add kernel (pv_psola_process_device), 2^24 outputs mono, periods 192 .. 208 samples moved by 1.25; a
+launch includes the host's validation of the grain table, the walk that finds every tile's grains and the upload of both.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola]
 """
 import argparse
 import json
@@ -195,6 +197,24 @@ def f0_line(torch, phaze_amd, W, hop, lo, ML, nch, T, steps, warmup):
             "hbm_fraction": frames * (hop * 4 + 16) / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def psola_line(torch, phaze_amd, n, ratio, steps, warmup):
+    hop = 256
+    nrec = n // hop
+    lag = 200 + (np.arange(nrec) // 64) % 17 - 8                       # periods 192 .. 208 samples, a new one every 64 records
+    records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)      # + 0.184 by the parabola
+    grains = phaze_amd.psola_plan(records, hop, hop // 2, n, 256.0, 32, 1024, np.full(nrec, ratio))
+    x = (torch.rand((1, n), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, n), device="cuda")
+    ps = phaze_amd.Psola(1024, max_channels=1, max_outputs=1024)
+    stream = torch.cuda.Stream()
+    ps.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ps.process_device(x.data_ptr(), n, n, 1, grains, y.data_ptr(), 0, n, n), steps, warmup)
+    ps.close()
+    return {"kernel": "pv_psola", "max_period": 1024, "ratio": ratio, "channels": 1, "outputs": n, "grains": int(grains.shape[0]), "ms_per_launch": round(ms, 4),
+            "outputs_per_s": n / (ms * 1e-3), "hbm_fraction": 2 * n * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -224,9 +244,14 @@ def main():
     ap.add_argument("--vari", action="store_true", help="add the variable-ratio resampler lines and the pitch-curve lines")
     ap.add_argument("--f0", action="store_true", help="only the f0 tracker lines")
     ap.add_argument("--f0-frames", type=int, default=16384, help="frames per channel of the f0 lines")
+    ap.add_argument("--psola", action="store_true", help="only the pitch-synchronous overlap-add line")
+    ap.add_argument("--psola-outputs", type=int, default=1 << 24, help="outputs of the overlap-add line")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.psola:
+        print(json.dumps(psola_line(torch, phaze_amd, args.psola_outputs, 1.25, args.steps, args.warmup)), flush=True)
+        return
     if args.f0:
         for nch in (1, 8):
             print(json.dumps(f0_line(torch, phaze_amd, 1024, 256, 32, 1024, nch, args.f0_frames, args.steps, args.warmup)), flush=True)

@@ -54,7 +54,7 @@ typedef struct pv_handle pv_handle;
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
- *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*. */
+ *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -666,8 +666,8 @@ PV_API int64_t pv_tune_plan(const pv_tune_params *p, const int32_t *records, int
 /* ---- formant-preserving pitch correction: pitch-synchronous overlap-add (TD-PSOLA) on a grain table ------------------------------------ */
 /* For a monophonic voice.  Two-period Hann grains are cut at the pitch period, re-spaced at period / ratio and overlap-added: a grain keeps the
  * vocal tract's response, so the spectral envelope stays where it was and only the spacing, the pitch, moves; duration is kept by construction.
- * The marks are spaced at the period but NOT aligned to the glottal epochs (DESIGN.md "Pitch-synchronous correction" has the measured cost), and
- * one grain table serves every channel of a call, so a stereo pair keeps its image.
+ * The marks are spaced at the period, and aligned to the glottal epochs when the plan is made with epoch records (pv_epoch_plan below; DESIGN.md
+ * "Pitch-synchronous correction" has the measured cost of unaligned marks), and one grain table serves every channel of a call, so a stereo pair keeps its image.
  * A grain is four int32 {t, tf, dq, L}: a Hann window of half length L samples centred at output position t + tf / 256 (tf in 0 .. 255) over the
  * input shifted by dq / 256 samples, i.e. output n of the grain reads the input at the real position n - dq / 256.  2 <= L <= max_period <= 4096,
  * |dq| <= 256 max_period, centres non-decreasing, positions relative to the buffer and below 2^30.  For output n and grain g:
@@ -741,6 +741,71 @@ typedef struct pv_psola_params {
 /* Returns the number of grains planned and writes at most `capacity` of them (four int32 each; the two-call sizing of pv_transient_plan).  records:
  * nrec records of one channel; ratios: nrec values within [1/2, 2] or NULL.  -PV_ERR_ARGUMENT for an argument out of range. */
 PV_API int64_t pv_psola_plan(const pv_psola_params *p, const int32_t *records, int64_t nrec, const double *ratios, int32_t *grains, int64_t capacity);
+
+/* ---- epoch marks for the overlap-add path: where the pitch pulses sit (a separate handle) and the planner that puts the analysis marks there ---- */
+/* A comb of short-time energy steps at the pitch period, on block-scaled integers: every value of a record is an exact integer function of the frame's
+ * samples and of its period, whatever the tiling.  Per channel, frame m reads the `window` samples x[m hop, m hop + window) and nothing else: no
+ * padding, no carried state; and one int32 p = periods256[m], the period in 1/256 sample (pv_epoch_periods makes the row from f0 records; one row
+ * serves all channels, as the grain table does).  8 <= max_period <= 2048, 2 max_period <= window <= 8192, 1 <= hop <= 4096.
+ *   scale    A = max |x_i| in f32; a non-finite sample, A == 0 or a p outside [256 * 8, 256 max_period] give the record {0, 0, 0, 0} (such a p is data,
+ *            not an error).  Else A = f 2^e with f in [0.5, 1) and q_i = rint(x_i 2^(10 - e)), exactly scaled, ties to even: |q_i| <= 1024.
+ *   sizes    w = max(2, p >> 10), a quarter period; Pc = (p + 255) >> 8; S(a, b) = sum_{a <= i < b} q_i^2.
+ *   rise     D[n] = S(n, n + w) - S(n - w, n), the step in short-time energy at n, and the mass M[n] = S(n - w, n + w), for w <= n <= window - w.
+ *   comb     K = the number of k >= 0 with w + Pc - 1 + ((k p) >> 8) <= window - w (at least 1);
+ *            C(phi) = sum_{k < K} D[w + phi + ((k p) >> 8)] for phi = 0 .. Pc - 1, in int64; phi* is the first argmax.
+ *   record   {w + phi*, K, w, s}: the position in the frame of the first pulse found, the teeth summed, the quarter period, and the strength
+ *            s = (max(C(phi*), 0) 2^14) div Mtot, Mtot = sum_{k < K} M[w + phi* + ((k p) >> 8)], s = 0 when Mtot == 0; 0 <= s <= 16384.
+ * A record is four int32.  The position trails the pulse of a voice by a few samples, the same few at every phase (DESIGN.md "Epoch marks"). */
+typedef struct pv_epoch_config {
+    int32_t struct_size;     /* sizeof(pv_epoch_config) as the caller compiled it (PV_EPOCH_CONFIG_INIT sets it)                  */
+    int32_t window;          /* samples per frame                                                                                */
+    int32_t hop;             /* samples between frames: the f0 tracker's hop when the records go to pv_epoch_plan                */
+    int32_t max_period;      /* the longest period looked for, in samples                                                        */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_frames;      /* host-pointer calls: staging size in frames (0 => 256); longer calls go in pieces                 */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_epoch_config;
+#define PV_EPOCH_CONFIG_INIT { (int32_t)sizeof(pv_epoch_config), 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_epoch pv_epoch;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_epoch_last_error(NULL). */
+PV_API int pv_epoch_create(const pv_epoch_config *cfg, pv_epoch **out);
+PV_API int pv_epoch_destroy(pv_epoch *h);
+PV_API const char *pv_epoch_last_error(const pv_epoch *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_epoch_set_stream(pv_epoch *h, void *hip_stream);
+PV_API int pv_epoch_synchronize(pv_epoch *h);
+/* nframes frames of channels 0 .. nch-1: channel c reads in[c*in_stride .. + (nframes - 1) hop + window) and periods256[0 .. nframes) and writes nframes
+ * records to records[4 (c*rec_stride + m) ..): rec_stride counts records.  Rejected with PV_ERR_ARGUMENT before any device work and with the records
+ * untouched: a null buffer, a negative count and, with nch > 1, strides below what a channel reads and writes.  nch > max_channels: PV_ERR_CAPACITY.
+ * Host pointers, synchronous, staged in pieces of max_frames. */
+PV_API int pv_epoch_track(pv_epoch *h, const float *in, int32_t nch, int64_t nframes, int64_t in_stride, const int32_t *periods256, int32_t *records,
+                          int64_t rec_stride);
+/* The same on DEVICE in / periods / records pointers (records 16-byte aligned: a record is one store), asynchronous on the handle's stream. */
+PV_API int pv_epoch_track_device(pv_epoch *h, const float *d_in, int32_t nch, int64_t nframes, int64_t in_stride, const int32_t *d_periods256,
+                                 int32_t *d_records, int64_t rec_stride);
+/* Pure host code.  The period row of pv_epoch_track from f0 records: periods256[j] = floor(256 pv_f0_period(record j) + 1/2), 0 where it is unvoiced or
+ * empty.  Returns nrec and writes at most `capacity` values (the two-call sizing of pv_transient_plan); -PV_ERR_ARGUMENT for an argument out of range. */
+PV_API int64_t pv_epoch_periods(const int32_t *records, int64_t nrec, int32_t *periods256, int64_t capacity);
+
+/* pv_psola_plan with its analysis marks on the pulses.  epochs: nrec epoch records, record j belonging to f0 record j with its position relative to
+ * j f0_hop (an epoch handle run at the tracker's hop on the same buffer), or NULL.  Everything is pv_psola_plan's but the analysis marks:
+ * A_0 = snap(0, none), A_(i+1) = snap(A_i + P(A_i), A_i).  snap(c, prev), with j = rec(c): c itself when epochs is NULL, f0 record j is unvoiced,
+ * K_j <= 0 or s_j < min_strength.  Else P = P(c), E = j f0_hop + pos_j and s = E + floor((c - E) / P + 1/2) P, the lattice point nearest c; when prev is
+ * given and s - prev < P / 2, s += P; when prev is given, voiced(prev) and |s - c| <= P / 4, s = c + lock (s - c): a first-order lock, so that the
+ * half-sample quantisation of the records does not become mark jitter, while a larger disagreement and the first voiced mark after an unvoiced one
+ * snap at once.  With epochs == NULL the grains are pv_psola_plan's bit for bit.  Centres are strictly ascending and |dq| <= 256 max_period. */
+typedef struct pv_epoch_params {
+    int32_t struct_size;     /* sizeof(pv_epoch_params) as the caller compiled it (PV_EPOCH_PARAMS_INIT sets it)                  */
+    int32_t min_strength;    /* 0 .. 16384: records with a smaller s leave their marks where pv_psola_plan puts them             */
+    double lock;             /* (0, 1]: how much of a small correction one mark takes; 1 snaps every mark                        */
+} pv_epoch_params;
+#define PV_EPOCH_PARAMS_INIT { (int32_t)sizeof(pv_epoch_params), 0, 0.125 }
+/* Returns the number of grains planned and writes at most `capacity` of them, as pv_psola_plan.  -PV_ERR_ARGUMENT for an argument out of range. */
+PV_API int64_t pv_epoch_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
+                             const int32_t *epochs, int32_t *grains, int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,8 @@ EXPORTS = [
     "pv_tune_plan",
     "pv_psola_create", "pv_psola_destroy", "pv_psola_last_error", "pv_psola_set_stream", "pv_psola_synchronize", "pv_psola_process",
     "pv_psola_process_device", "pv_psola_window", "pv_psola_ratios", "pv_psola_plan",
+    "pv_epoch_create", "pv_epoch_destroy", "pv_epoch_last_error", "pv_epoch_set_stream", "pv_epoch_synchronize", "pv_epoch_track", "pv_epoch_track_device",
+    "pv_epoch_periods", "pv_epoch_plan",
 ]
 
 
@@ -92,6 +94,24 @@ class _PsolaConfig(C.Structure):
 class _PsolaParams(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("struct_size", "f0_hop", "f0_center", "min_period", "max_period", "reserved")]
                 + [("unvoiced_period", C.c_double), ("input_len", C.c_int64)])
+
+
+class _EpochConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "window", "hop", "max_period", "max_channels", "max_frames", "device_id", "flags")]
+
+
+class _EpochParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("min_strength", C.c_int32), ("lock", C.c_double)]
+
+
+def make_epoch_config(window, hop, max_period, max_channels=1, max_frames=0, device_id=0, flags=0):
+    """pv_epoch_config with struct_size filled in (the C side's PV_EPOCH_CONFIG_INIT)."""
+    return _EpochConfig(C.sizeof(_EpochConfig), window, hop, max_period, max_channels, max_frames, device_id, flags)
+
+
+def make_epoch_params(min_strength=0, lock=0.125):
+    """pv_epoch_params with struct_size filled in (the C side's PV_EPOCH_PARAMS_INIT)."""
+    return _EpochParams(C.sizeof(_EpochParams), min_strength, lock)
 
 
 def make_psola_config(max_period, max_channels=1, max_outputs=0, device_id=0, flags=0):
@@ -303,6 +323,15 @@ def load_library():
     L.pv_psola_window.argtypes = [fp, C.c_int64]
     L.pv_psola_ratios.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, C.POINTER(C.c_double), C.c_int64]
     L.pv_psola_plan.argtypes = [C.POINTER(_PsolaParams), ip, C.c_int64, C.POINTER(C.c_double), ip, C.c_int64]
+    L.pv_epoch_create.argtypes = [C.POINTER(_EpochConfig), C.POINTER(vp)]
+    L.pv_epoch_destroy.argtypes = [vp]
+    L.pv_epoch_last_error.argtypes = [vp]
+    L.pv_epoch_set_stream.argtypes = [vp, vp]
+    L.pv_epoch_synchronize.argtypes = [vp]
+    L.pv_epoch_track.argtypes = [vp, fp, C.c_int32, C.c_int64, C.c_int64, ip, ip, C.c_int64]
+    L.pv_epoch_track_device.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, C.c_int64]
+    L.pv_epoch_periods.argtypes = [ip, C.c_int64, ip, C.c_int64]
+    L.pv_epoch_plan.argtypes = [C.POINTER(_PsolaParams), C.POINTER(_EpochParams), ip, C.c_int64, C.POINTER(C.c_double), ip, ip, C.c_int64]
     for n in EXPORTS:
         if n not in ("pv_last_error", "pv_status_string", "pv_stretch_last_error"):
             getattr(L, n).restype = C.c_int
@@ -319,6 +348,8 @@ def load_library():
     L.pv_tune_plan.restype = C.c_int64
     L.pv_psola_last_error.restype = C.c_char_p
     L.pv_psola_window.restype = L.pv_psola_ratios.restype = L.pv_psola_plan.restype = C.c_int64
+    L.pv_epoch_last_error.restype = C.c_char_p
+    L.pv_epoch_periods.restype = L.pv_epoch_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1394,10 +1425,11 @@ class Psola(_Handle):
         self._check(self._L.pv_psola_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng,
                                                     C.c_void_p(d_out), out_first, nout, out_stride))
 
-    def process_tuned(self, x, sample_rate, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0):
+    def process_tuned(self, x, sample_rate, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0, epochs=False):
         """Offline formant-preserving pitch correction onto a scale: F0Tracker.track (channel 0: one plan for all channels) -> tune_ratios -> psola_plan
-        -> process.  x: float32[nch, n] (host).  tracker: an F0Tracker, default window 1024, hop 256, min_lag 32 and max_lag = max_period.  Returns
-        (y of the shape of x, grains)."""
+        -> process.  x: float32[nch, n] (host).  tracker: an F0Tracker, default window 1024, hop 256, min_lag 32 and max_lag = max_period.  epochs=True
+        puts the analysis marks on the pitch pulses: an EpochTracker at the tracker's hop (longest period min(max_lag, 2048, span // 2), window twice
+        that, span = the tracker's window + max_lag) -> epoch_plan in place of psola_plan.  Returns (y of the shape of x, grains)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         one = x.ndim == 1
         if one:
@@ -1413,7 +1445,100 @@ class Psola(_Handle):
                 tracker.close()
         ratios = tune_ratios(records, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
         min_period = tracker.min_lag
-        grains = psola_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
-                            self.max_period, ratios)
+        plan_args = (records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                     self.max_period, ratios)
+        if epochs:
+            longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
+            marks = EpochTracker(2 * longest, tracker.hop, longest)
+            try:
+                found = marks.track(x[0], epoch_periods(records))[0]
+            finally:
+                marks.close()
+            grains = epoch_plan(*plan_args, epochs=found)
+        else:
+            grains = psola_plan(*plan_args)
         y = self.process(x, grains)
         return (y[0] if one else y), grains
+
+
+def epoch_periods(records):
+    """pv_epoch_periods: the int32 period row of EpochTracker.track from the f0 records int32[nrec, 4] of ONE channel: floor(256 period + 1/2), 0 where
+    a record is unvoiced or empty."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    out = np.zeros(nrec, np.int32)
+    ip = C.POINTER(C.c_int32)
+    if L.pv_epoch_periods(r.ctypes.data_as(ip) if nrec else None, nrec, out.ctypes.data_as(ip) if nrec else None, nrec) != nrec:
+        raise ValueError("epoch_periods: bad argument")
+    return out
+
+
+def epoch_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None, epochs=None, min_strength=0, lock=0.125):
+    """pv_epoch_plan: psola_plan with the analysis marks on the pitch pulses.  epochs: int32[nrec, 4] of EpochTracker.track run at the tracker's hop on the
+    same buffer (record j belongs to f0 record j), or None: then the grains are psola_plan's.  min_strength 0 .. 16384: weaker records leave their marks
+    alone; lock (0, 1]: how much of a small correction one mark takes."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    rho = None
+    if ratios is not None:
+        rho = np.ascontiguousarray(ratios, dtype=np.float64)
+        if rho.shape != (nrec,):
+            raise ValueError("ratios must be float64[nrec]")
+    ep = None
+    if epochs is not None:
+        ep = np.ascontiguousarray(epochs, dtype=np.int32)
+        if ep.shape != (nrec, 4) and not (nrec == 0 and ep.size == 0):
+            raise ValueError("epochs must be int32[nrec, 4]: one record per f0 record")
+    p = make_psola_params(int(f0_hop), int(f0_center), int(input_len), float(unvoiced_period), int(min_period), int(max_period))
+    e = make_epoch_params(int(min_strength), float(lock))
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rp = r.ctypes.data_as(ip) if nrec else None
+    qp = rho.ctypes.data_as(dp) if rho is not None and nrec else None
+    ep_ = ep.ctypes.data_as(ip) if ep is not None and nrec else None
+    n = L.pv_epoch_plan(C.byref(p), C.byref(e), rp, nrec, qp, ep_, None, 0)
+    if n < 0:
+        raise ValueError("epoch_plan: bad argument (psola_plan's ranges, 0 <= min_strength <= 16384, 0 < lock <= 1)")
+    grains = np.zeros((n, 4), np.int32)
+    if n:
+        L.pv_epoch_plan(C.byref(p), C.byref(e), rp, nrec, qp, ep_, grains.ctypes.data_as(ip), n)
+    return grains
+
+
+class EpochTracker(_Handle):
+    """The epoch records (pv_epoch_*): where in a frame the pitch pulses sit.  Frame m of a channel reads x[m hop, m hop + window) and the period
+    periods256[m] in 1/256 sample (one row for all channels; epoch_periods makes it from f0 records) and gives one record int32[4] =
+    {position of the first pulse found, teeth summed, quarter period, strength 0 .. 16384}; all zeros for silence, a non-finite sample or a period outside
+    [8, max_period].  Stateless: a stream analysed in pieces overlaps them by window - hop samples."""
+
+    _prefix = "pv_epoch"
+    _fft_size_is_value_error = False
+
+    def __init__(self, window, hop, max_period, max_channels=1, max_frames=256, device_id=0):
+        self._create(make_epoch_config(window, hop, max_period, max_channels, max_frames, device_id, 0))
+        self.window, self.hop, self.max_period, self.max_channels = window, hop, max_period, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no state."""
+
+    def frames(self, n):
+        """How many frames fit n samples per channel."""
+        return max((n - self.window) // self.hop + 1, 0)
+
+    def track(self, x, periods256):
+        """x: float32[nch, n] (host), periods256: int32[nframes] with nframes <= frames(n) -> int32[nch, nframes, 4]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        per = np.ascontiguousarray(periods256, dtype=np.int32)
+        if per.ndim != 1 or per.size > self.frames(n):
+            raise ValueError("periods256 must be int32[nframes] with nframes <= frames(n)")
+        nframes = per.size
+        rec = np.zeros((nch, nframes, 4), np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.pv_epoch_track(self._h, _fp(x), nch, nframes, n, per.ctypes.data_as(ip), rec.ctypes.data_as(ip), nframes))
+        return rec
+
+    def track_device(self, d_in, nch, nframes, in_stride, d_periods256, d_records, rec_stride):
+        """pv_epoch_track_device on raw device pointers (ints), asynchronous on the handle's stream; rec_stride counts records."""
+        self._check(self._L.pv_epoch_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, C.c_void_p(d_periods256), C.c_void_p(d_records), rec_stride))

@@ -19,8 +19,10 @@ With --f0: only the f0 tracker (pv_f0_track_device) at W = 1024, max_lag = 1024,
 channel of a harmonic tone; frames/s counts channel-frames, and `macs_per_s` is frames/s times the W * max_lag multiply-adds of a frame's lag products.
 With --psola: only the pitch-synchronous overlap-add kernel (pv_psola_process_device), 2^24 outputs mono, periods 192 .. 208 samples moved by 1.25; a
 launch includes the host's validation of the grain table, the walk that finds every tile's grains and the upload of both.
+With --epoch: only the epoch kernel (pv_epoch_track_device) at window 2048, hop 256, longest period 1024, mono and 8 channels, --f0-frames frames per
+channel of a pulse train of period 217.3; frames/s counts channel-frames.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch]
 """
 import argparse
 import json
@@ -197,6 +199,24 @@ def f0_line(torch, phaze_amd, W, hop, lo, ML, nch, T, steps, warmup):
             "hbm_fraction": frames * (hop * 4 + 16) / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def epoch_line(torch, phaze_amd, window, hop, max_period, nch, T, steps, warmup):
+    n = (T - 1) * hop + window
+    k = torch.arange(n, device="cuda", dtype=torch.float32)
+    x = torch.stack([torch.exp(-torch.remainder(k + 31 * c, 217.3) / 40.0) * torch.cos(2 * np.pi * torch.remainder(k + 31 * c, 217.3) / 40.0) for c in range(nch)]).contiguous() * 0.8
+    per = torch.full((T,), int(217.3 * 256), dtype=torch.int32, device="cuda")
+    rec = torch.empty((nch, T, 4), dtype=torch.int32, device="cuda")
+    trk = phaze_amd.EpochTracker(window, hop, max_period, max_channels=nch, max_frames=1)
+    stream = torch.cuda.Stream()
+    trk.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: trk.track_device(x.data_ptr(), nch, T, n, per.data_ptr(), rec.data_ptr(), T), steps, warmup)
+    trk.close()
+    found = int((rec[:, :, 1] > 0).sum().item())
+    frames = nch * T
+    return {"kernel": "pv_epoch", "window": window, "hop": hop, "max_period": max_period, "channels": nch, "frames_per_channel": T, "frames_found": found,
+            "ms_per_launch": round(ms, 4), "frames_per_s": frames / (ms * 1e-3), "hbm_fraction": frames * (hop * 4 + 16) / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def psola_line(torch, phaze_amd, n, ratio, steps, warmup):
     hop = 256
     nrec = n // hop
@@ -246,11 +266,16 @@ def main():
     ap.add_argument("--f0-frames", type=int, default=16384, help="frames per channel of the f0 lines")
     ap.add_argument("--psola", action="store_true", help="only the pitch-synchronous overlap-add line")
     ap.add_argument("--psola-outputs", type=int, default=1 << 24, help="outputs of the overlap-add line")
+    ap.add_argument("--epoch", action="store_true", help="only the epoch kernel lines (--f0-frames frames per channel)")
     args = ap.parse_args()
     import torch
     import phaze_amd
     if args.psola:
         print(json.dumps(psola_line(torch, phaze_amd, args.psola_outputs, 1.25, args.steps, args.warmup)), flush=True)
+        return
+    if args.epoch:
+        for nch in (1, 8):
+            print(json.dumps(epoch_line(torch, phaze_amd, 2048, 256, 1024, nch, args.f0_frames, args.steps, args.warmup)), flush=True)
         return
     if args.f0:
         for nch in (1, 8):

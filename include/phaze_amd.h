@@ -54,7 +54,7 @@ typedef struct pv_handle pv_handle;
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
- *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*. */
+ *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -806,6 +806,67 @@ typedef struct pv_epoch_params {
 /* Returns the number of grains planned and writes at most `capacity` of them, as pv_psola_plan.  -PV_ERR_ARGUMENT for an argument out of range. */
 PV_API int64_t pv_epoch_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
                              const int32_t *epochs, int32_t *grains, int64_t capacity);
+
+/* ---- time-scale modification on the overlap-add path: the output runs at another speed than the input, pitch and formants stay (a separate handle) ---- */
+/* TD-PSOLA's duration half.  pv_psola_process writes every grain near where it reads (|dq| <= 256 max_period): the output is as long as the input.
+ * Here a grain reads the input anywhere.  A far grain is four int32 {t, w, D, L} with w = tf + 256 phi, tf and phi in 0 .. 255: a Hann window of half
+ * length L centred at output position t + tf / 256; output n of the grain reads the input at the real position n - D - phi / 256.  D is any whole number
+ * with |D| < 2^30: it stands where pv_psola's dq div 256 stands, and phi where its dq mod 256.  2 <= L <= max_period, 0 <= t < 2^30, centres
+ * non-decreasing.  The window, sample and output rules are pv_psola_process's word for word (the same Hn and P; phi == 0 reads x[n - D] itself, else
+ * theta = 256 - phi, b = n - D - 1 and 64 taps; num and den in grain order; x is 0 outside [0, nin)), so a table whose grains all have
+ * |256 D + phi| <= 256 max_period is pv_psola_process's table in another notation and gives its bits.  The order of every sum is a function of (g, i)
+ * alone: any partition of the output range into calls gives the same bits.
+ * What a call may read: its outputs go in tiles of 1024 from out_first on, and the input samples that the grains reaching one tile [j0, j1) read inside it,
+ * from min (max(j0, t - L) - D - 33) to max (min(j1, t + L) - D + 32), must not be more than
+ * span(max_period, max_rate) = max_rate (1024 + 2 max_period) + 4 max_period + 64.  A table of pv_tsm_plan whose rates lie within
+ * [1 / max_rate, max_rate] keeps to it (DESIGN.md "Time-scale modification"); a call with a tile beyond it is refused.  The span, the prototype and the
+ * window table share the 160 KiB of LDS of a compute unit: pv_tsm_create returns PV_ERR_UNSUPPORTED for a pair beyond that (max_period 4096 goes with
+ * max_rate 1 only, 2048 and less with any).
+ * Limits: for a monophonic voice; one plan serves all channels; unvoiced grains repeated at slow rates can buzz (their time direction is not alternated). */
+typedef struct pv_tsm_config {
+    int32_t struct_size;     /* sizeof(pv_tsm_config) as the caller compiled it (PV_TSM_CONFIG_INIT sets it)                      */
+    int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096                                             */
+    int32_t max_rate;        /* 1 .. 4: sizes the span; plans whose rates lie within [1 / max_rate, max_rate] fit                */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_tsm_config;
+#define PV_TSM_CONFIG_INIT { (int32_t)sizeof(pv_tsm_config), 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_tsm pv_tsm;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_tsm_last_error(NULL). */
+PV_API int pv_tsm_create(const pv_tsm_config *cfg, pv_tsm **out);
+PV_API int pv_tsm_destroy(pv_tsm *h);
+PV_API const char *pv_tsm_last_error(const pv_tsm *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_tsm_set_stream(pv_tsm *h, void *hip_stream);
+PV_API int pv_tsm_synchronize(pv_tsm *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1: channel c reads in[c*in_stride .. + nin) and writes out[c*out_stride .. + nout),
+ * out[0] being output out_first; nout is the caller's (pv_tsm_plan's output_len for a whole signal).  grains: ngrains far grains on the HOST, one table
+ * for all channels.  Stateless.  Rejected with PV_ERR_ARGUMENT before any device work and with the output untouched: a null buffer, a negative count, a
+ * position of 2^30 or more, with nch > 1 strides below nin / nout, a grain out of range or out of order, and a tile that reads more than the span (the
+ * message names the grain, for a tile its first).  nch > max_channels: PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of max_outputs
+ * or less: a piece stages the input range its tiles read, and is one tile where more would not fit the staging buffer. */
+PV_API int pv_tsm_process(pv_tsm *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains, float *out,
+                          int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains stay a host table), asynchronous on the handle's stream. */
+PV_API int pv_tsm_process_device(pv_tsm *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains,
+                                 float *d_out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* Pure host code: pv_epoch_plan with a read position V beside the synthesis position T, V_0 = T_0 = 0.  rates: nrec values, rates[j] the input samples
+ * consumed per output sample while V lies on record j (2 plays twice as fast, 1/2 at half speed), finite and positive, held within [1/4, 4], voiced or
+ * not; NULL: 1.  Everything is pv_epoch_plan's (rec, P, rho, snap, the marks A_i, the monotone walk, c / t / tf / L of a grain, cap) with two
+ * differences: the loop runs while V < input_len, and the walk takes the mark nearest V, with step, voiced, rho and rate evaluated at V.  After a grain
+ * is held, s = min(P(V) / rho(V), cap), T += s, V += rate(V) s.  A grain has dq = floor(256 (T - A) + 1/2) in int64, D = dq div 256, phi = dq mod 256.
+ * Where a grain is held, neither V nor A is voiced and A < input_len: Tn = A + rint((T + (A - V)) - A), and if A >= Vprev + 1, Tn >= Tprev + 1 and
+ * Tn - Tprev <= cap then T = Tn, V = A: unvoiced material passes as whole-sample copies at any rate (there the rate is realised as a pattern of mark
+ * reuse, exactly where it or its inverse is whole).  *output_len (may be NULL) = floor(T + (input_len - V) / rate(V) + 1/2) for the last grain's T
+ * and V, 0 without grains.  With rates == NULL the grains are pv_epoch_plan's in the far notation, bit for bit, and output_len == input_len.
+ * Returns the number of grains and writes at most `capacity` of them, as pv_psola_plan; -PV_ERR_ARGUMENT for an argument out of range, and when a
+ * centre would reach 2^30 (grains before it may have been written). */
+PV_API int64_t pv_tsm_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
+                           const double *rates, const int32_t *epochs, int32_t *grains, int64_t capacity, int64_t *output_len);
 
 #ifdef __cplusplus
 }

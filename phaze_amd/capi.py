@@ -44,6 +44,7 @@ EXPORTS = [
     "pv_psola_process_device", "pv_psola_window", "pv_psola_ratios", "pv_psola_plan",
     "pv_epoch_create", "pv_epoch_destroy", "pv_epoch_last_error", "pv_epoch_set_stream", "pv_epoch_synchronize", "pv_epoch_track", "pv_epoch_track_device",
     "pv_epoch_periods", "pv_epoch_plan",
+    "pv_tsm_create", "pv_tsm_destroy", "pv_tsm_last_error", "pv_tsm_set_stream", "pv_tsm_synchronize", "pv_tsm_process", "pv_tsm_process_device", "pv_tsm_plan",
 ]
 
 
@@ -102,6 +103,15 @@ class _EpochConfig(C.Structure):
 
 class _EpochParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("min_strength", C.c_int32), ("lock", C.c_double)]
+
+
+class _TsmConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+def make_tsm_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_tsm_config with struct_size filled in (the C side's PV_TSM_CONFIG_INIT)."""
+    return _TsmConfig(C.sizeof(_TsmConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
 
 
 def make_epoch_config(window, hop, max_period, max_channels=1, max_frames=0, device_id=0, flags=0):
@@ -350,6 +360,17 @@ def load_library():
     L.pv_psola_window.restype = L.pv_psola_ratios.restype = L.pv_psola_plan.restype = C.c_int64
     L.pv_epoch_last_error.restype = C.c_char_p
     L.pv_epoch_periods.restype = L.pv_epoch_plan.restype = C.c_int64
+    L.pv_tsm_create.argtypes = [C.POINTER(_TsmConfig), C.POINTER(vp)]
+    L.pv_tsm_destroy.argtypes = [vp]
+    L.pv_tsm_last_error.argtypes = [vp]
+    L.pv_tsm_set_stream.argtypes = [vp, vp]
+    L.pv_tsm_synchronize.argtypes = [vp]
+    L.pv_tsm_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_tsm_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_tsm_plan.argtypes = [C.POINTER(_PsolaParams), C.POINTER(_EpochParams), ip, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), ip, ip, C.c_int64,
+                              C.POINTER(C.c_int64)]
+    L.pv_tsm_last_error.restype = C.c_char_p
+    L.pv_tsm_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1542,3 +1563,118 @@ class EpochTracker(_Handle):
     def track_device(self, d_in, nch, nframes, in_stride, d_periods256, d_records, rec_stride):
         """pv_epoch_track_device on raw device pointers (ints), asynchronous on the handle's stream; rec_stride counts records."""
         self._check(self._L.pv_epoch_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, C.c_void_p(d_periods256), C.c_void_p(d_records), rec_stride))
+
+
+def tsm_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None, rates=None, epochs=None, min_strength=0, lock=0.125):
+    """pv_tsm_plan: (far grains int32[ngrains, 4] = {t, tf + 256 phi, D, L} of Tsm.process, output_len).  epoch_plan with a read position beside the
+    synthesis position: rates float64[nrec], the input samples consumed per output sample while the read position lies on record j (2: twice as fast,
+    1/2: half speed; finite and positive, held within [1/4, 4]; None: 1, and then the grains are epoch_plan's in the far notation)."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    rows = []
+    for name, row in (("ratios", ratios), ("rates", rates)):
+        if row is not None:
+            row = np.ascontiguousarray(row, dtype=np.float64)
+            if row.shape != (nrec,):
+                raise ValueError(f"{name} must be float64[nrec]")
+        rows.append(row)
+    rho, spd = rows
+    ep = None
+    if epochs is not None:
+        ep = np.ascontiguousarray(epochs, dtype=np.int32)
+        if ep.shape != (nrec, 4) and not (nrec == 0 and ep.size == 0):
+            raise ValueError("epochs must be int32[nrec, 4]: one record per f0 record")
+    p = make_psola_params(int(f0_hop), int(f0_center), int(input_len), float(unvoiced_period), int(min_period), int(max_period))
+    e = make_epoch_params(int(min_strength), float(lock))
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rp = r.ctypes.data_as(ip) if nrec else None
+    qp = rho.ctypes.data_as(dp) if rho is not None and nrec else None
+    sp = spd.ctypes.data_as(dp) if spd is not None and nrec else None
+    ep_ = ep.ctypes.data_as(ip) if ep is not None and nrec else None
+    out_len = C.c_int64(0)
+    n = L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, None, 0, C.byref(out_len))
+    if n < 0:
+        raise ValueError("tsm_plan: bad argument (epoch_plan's ranges, rates finite and positive, and the output must end below 2^30)")
+    grains = np.zeros((n, 4), np.int32)
+    if n:
+        L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, grains.ctypes.data_as(ip), n, C.byref(out_len))
+    return grains, int(out_len.value)
+
+
+class Tsm(_Handle):
+    """Time-scale modification by pitch-synchronous overlap-add (pv_tsm_*): the tempo of a monophonic voice changes, pitch and formants stay (and the pitch
+    may be corrected in the same pass).  A far grain int32[4] = {t, tf + 256 phi, D, L} is a Hann window of half length L centred at output position
+    t + tf / 256 that reads the input at n - D - phi / 256, anywhere; one table serves every channel.  A tile of 1024 outputs may read
+    max_rate (1024 + 2 max_period) + 4 max_period + 64 input samples: tsm_plan's tables at rates within [1 / max_rate, max_rate] keep to that.  Stateless:
+    outputs [out_first, out_first + nout) are a pure function of (x, grains), and any partition of the range gives the same bits; on a table that reads near
+    where it writes they are Psola.process's bits."""
+
+    _prefix = "pv_tsm"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_tsm_config(max_period, max_rate, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_channels = max_period, max_rate, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    _grains = staticmethod(Psola._grains)
+
+    def process(self, x, grains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), grains: int32[ngrains, 4] -> float32[nch, nout], outputs out_first .. out_first + nout - 1 (default: n - out_first; pass
+        tsm_plan's output_len for a whole stretched signal)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        g, ng = self._grains(grains)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_tsm_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng, _fp(y), int(out_first), nout,
+                                           max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, grains, d_out, out_first, nout, out_stride):
+        """pv_tsm_process_device on raw device pointers (ints), asynchronous on the handle's stream; grains is a host table."""
+        g, ng = self._grains(grains)
+        self._check(self._L.pv_tsm_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng,
+                                                  C.c_void_p(d_out), out_first, nout, out_stride))
+
+    def process_tuned(self, x, sample_rate, rate=1.0, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0, epochs=False):
+        """Offline tempo change of a monophonic voice: F0Tracker.track (channel 0: one plan for all channels) -> tune_ratios -> tsm_plan -> process.
+        rate: the input samples consumed per output sample, one number or one per f0 record (float64[nrec]: a tempo curve); 1/2 is half speed.
+        The voice is corrected onto the scale in the same pass, as Psola.process_tuned does; strength = 0 leaves the pitch alone.  tracker and epochs as
+        there.  x: float32[nch, n] (host).  Returns (y float32[nch, output_len], grains)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        own = tracker is None
+        if own:
+            max_lag = max(self.max_period, 3)
+            tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
+        try:
+            records = tracker.track(x[0], threshold)[0]
+        finally:
+            if own:
+                tracker.close()
+        nrec = records.shape[0]
+        ratios = tune_ratios(records, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+        rates = np.full(nrec, float(rate)) if np.ndim(rate) == 0 else np.ascontiguousarray(rate, dtype=np.float64)
+        if rates.shape != (nrec,):
+            raise ValueError(f"rate must be one number or one per f0 record ({nrec})")
+        min_period = tracker.min_lag
+        found = None
+        if epochs:
+            longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
+            marks = EpochTracker(2 * longest, tracker.hop, longest)
+            try:
+                found = marks.track(x[0], epoch_periods(records))[0]
+            finally:
+                marks.close()
+        grains, output_len = tsm_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                                      self.max_period, ratios=ratios, rates=rates, epochs=found)
+        y = self.process(x, grains, 0, output_len)
+        return (y[0] if one else y), grains

@@ -21,8 +21,11 @@ With --psola: only the pitch-synchronous overlap-add kernel (pv_psola_process_de
 launch includes the host's validation of the grain table, the walk that finds every tile's grains and the upload of both.
 With --epoch: only the epoch kernel (pv_epoch_track_device) at window 2048, hop 256, longest period 1024, mono and 8 channels, --f0-frames frames per
 channel of a pulse train of period 217.3; frames/s counts channel-frames.
+With --tsm: only the time-scale modification kernel (pv_tsm_process_device, max_period 1024, max_rate 2) on the --psola workload: 2^24 outputs mono,
+periods 192 .. 208 moved by 1.25, at the rates 1, 1/2 and 2 (the input is rate times as long as the output); the --psola line runs first in the same
+process: at rate 1 the two kernels do the same arithmetic on the same table.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm]
 """
 import argparse
 import json
@@ -235,6 +238,26 @@ def psola_line(torch, phaze_amd, n, ratio, steps, warmup):
             "outputs_per_s": n / (ms * 1e-3), "hbm_fraction": 2 * n * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def tsm_line(torch, phaze_amd, n, ratio, rate, steps, warmup):
+    hop = 256
+    nin = int(n * rate)
+    nrec = nin // hop
+    lag = 200 + (np.arange(nrec) // 64) % 17 - 8                       # psola_line's records
+    records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+    grains, nout = phaze_amd.tsm_plan(records, hop, hop // 2, nin, 256.0, 32, 1024, np.full(nrec, ratio), np.full(nrec, rate))
+    x = (torch.rand((1, nin), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, nout), device="cuda")
+    ts = phaze_amd.Tsm(1024, 2, max_channels=1, max_outputs=1024)
+    stream = torch.cuda.Stream()
+    ts.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: ts.process_device(x.data_ptr(), nin, nin, 1, grains, y.data_ptr(), 0, nout, nout), steps, warmup)
+    ts.close()
+    return {"kernel": "pv_tsm", "max_period": 1024, "max_rate": 2, "ratio": ratio, "rate": rate, "channels": 1, "inputs": nin, "outputs": nout,
+            "grains": int(grains.shape[0]), "ms_per_launch": round(ms, 4), "outputs_per_s": nout / (ms * 1e-3),
+            "hbm_fraction": (nin + nout) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -267,11 +290,17 @@ def main():
     ap.add_argument("--psola", action="store_true", help="only the pitch-synchronous overlap-add line")
     ap.add_argument("--psola-outputs", type=int, default=1 << 24, help="outputs of the overlap-add line")
     ap.add_argument("--epoch", action="store_true", help="only the epoch kernel lines (--f0-frames frames per channel)")
+    ap.add_argument("--tsm", action="store_true", help="only the overlap-add line and the time-scale modification lines at the rates 1, 1/2 and 2 (--psola-outputs outputs)")
     args = ap.parse_args()
     import torch
     import phaze_amd
     if args.psola:
         print(json.dumps(psola_line(torch, phaze_amd, args.psola_outputs, 1.25, args.steps, args.warmup)), flush=True)
+        return
+    if args.tsm:
+        print(json.dumps(psola_line(torch, phaze_amd, args.psola_outputs, 1.25, args.steps, args.warmup)), flush=True)
+        for rate in (1.0, 0.5, 2.0):
+            print(json.dumps(tsm_line(torch, phaze_amd, args.psola_outputs, 1.25, rate, args.steps, args.warmup)), flush=True)
         return
     if args.epoch:
         for nch in (1, 8):

@@ -68,11 +68,25 @@ def grain_weights(n, t, tf, L, Hn):
     return h, np.where(inside, np.abs(f * d), 0.0), nz
 
 
-def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=False):
+def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=False, subnormal=None):
     """x: float32[nch, nin], grains int[ngrains, 4] -> fp64[nch, nout], outputs out_first .. out_first + nout - 1.
     A non-finite sample counts as 0 in y; bound=True returns (y, tol, poisoned): tol the derived bound on |y_kernel - y| per sample
     (tests/test_gpu_psola.py states it) and poisoned the outputs that the kernel gives a non-finite value: those with a non-finite sample under a tap of
-    a grain with h != 0."""
+    a grain with h != 0.
+
+    The last term of tol covers roundings in the subnormal range.  The default, 2^-149 (1 + (G + 67) / D), is kept bit for bit; it is smaller than
+    the worst case below wherever D > about 2.2, which no test at O(1) amplitudes can see.  subnormal="derived" replaces it and returns
+    (y, tol, poisoned, G, den), G the number of grains covering an output and den = D = sum h_g.  DERIVATION.  A float32 result in the subnormal
+    range is within 2^-150 absolute of the exact one (half the spacing 2^-149) instead of within u relative, so every rounding is within
+    u |r| + 2^-150 and the absolute parts add up beside the relative bound.  The window weight h and the weight sum s of the taps are normal (h is 0
+    or above 2^-50, |s| = |d_g| about 1): only the signal path counts.  Per fractional grain, 64 fused multiply-adds into `a` give 64 2^-150, the
+    division a / s turns that into 64 2^-150 / |d_g| and rounds once more: |xt^ - xt| gains (64 / |d_g| + 1) 2^-150; a whole-sample grain reads the
+    sample itself and gains nothing.  The numerator takes G fused multiply-adds, G 2^-150, and carries sum |h_g| (64 / |d_g| + 1) 2^-150 =: Z 2^-150
+    from the grains; the quotient divides both by D and rounds once:
+        2^-150 ((Z + G) / D + 1)    to first order,
+    and one more unit of 2^-150 covers the second order (an absolute error scaled by the relative errors of h^, s^ and the weight sum, a factor
+    below 1 + (G + 70) u).  With every grain fractional and |d_g| >= 1, Z <= 65 D and the term is at most 2^-150 (G / D + 67), the hand count of
+    the same roundings; this one takes |d_g| from the table instead of assuming it and charges whole-sample grains nothing, so it is never larger."""
     x = np.asarray(x, np.float32)
     if x.ndim == 1:
         x = x[None, :]
@@ -89,6 +103,7 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
     badbuf[:, pad:pad + nin] = bad
     num = np.zeros((nch, nout)); den = np.zeros(nout)
     A = np.zeros((nch, nout)); S = np.zeros(nout); E = np.zeros((nch, nout)); G = np.zeros(nout, np.int64)
+    Z = np.zeros(nout)                                                    # sum |h_g| (64 / |d_g| + 1) over the fractional grains
     poisoned = np.zeros((nch, nout), bool)
     u = 2.0 ** -24
     i = np.arange(TAPS, dtype=np.int64)
@@ -123,6 +138,8 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
         A[:, sl] += m * np.abs(xt)
         S[sl] += m
         E[:, sl] += np.abs(h) * e
+        if phi != 0:
+            Z[sl] += np.abs(h) * (TAPS / abs(Dg) + 1.0)
         G[sl] += 1
         poisoned[:, sl] |= hit
     cov = G > 0
@@ -132,9 +149,14 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
         return y
     tol = np.zeros((nch, nout))
     Gc = (G[cov] + 3).astype(np.float64)
-    tol[:, cov] = ((u * Gc * (A[:, cov] + np.abs(y[:, cov]) * S[cov]) + E[:, cov]) / den[cov] + u * np.abs(y[:, cov])) * (1.0 + 2.0 ** -10) \
-        + 2.0 ** -149 * (1.0 + (Gc + TAPS) / den[cov])
-    return y, tol, poisoned
+    rel = ((u * Gc * (A[:, cov] + np.abs(y[:, cov]) * S[cov]) + E[:, cov]) / den[cov] + u * np.abs(y[:, cov])) * (1.0 + 2.0 ** -10)
+    if subnormal is None:
+        tol[:, cov] = rel + 2.0 ** -149 * (1.0 + (Gc + TAPS) / den[cov])
+        return y, tol, poisoned
+    if subnormal != "derived":
+        raise ValueError("subnormal: None or 'derived'")
+    tol[:, cov] = rel + 2.0 ** -150 * ((Z[cov] + G[cov]) / den[cov] + 2.0)
+    return y, tol, poisoned, G, den
 
 
 # ---- the planner ------------------------------------------------------------------------------------------------------------------------------

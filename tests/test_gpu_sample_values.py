@@ -13,7 +13,9 @@
    equal finite masks, in every cut; the output and both states are finite again from a position derived below.
 4. PitchGlide.process_tuned and TimeStretch.onset_strength with a bad sample: the frames that hold it give zero records / zero counts.
 5. Scaling by a power of two is exact: y(2^k x) == 2^k y(x) bit for bit for both resamplers at k = +-40 (the model checks that nothing leaves the
-   normal range), track(2^k x) == track(x) at k = +-20, +-100 and at a peak of FLT_MAX (the largest exponent)."""
+   normal range), track(2^k x) == track(x) at k = +-20, +-100 and at a peak of FLT_MAX (the largest exponent).
+6. The overlap-add path (pv_psola_*, pv_tsm_*, pv_epoch_*) has this axis in tests/test_gpu_ola_ranges.py: exact scaling up to 2^122, inputs in the
+   subnormal range against a derived bound, the epoch records under 2^k and at FLT_MAX, and positions and displacements up to 2^30 - 1."""
 import ctypes as C
 
 import numpy as np

@@ -115,10 +115,13 @@ def check_span(grains, max_period, max_rate, out_first, nout):
     return None
 
 
-def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=False):
+def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=False, subnormal=None):
     """x: float32[nch, nin], far grains int[ngrains, 4] -> fp64[nch, nout], outputs out_first .. out_first + nout - 1.  PM.process operation for
     operation (so that a near table gives its bits), with the input gathered at any distance.  bound=True returns (y, tol, poisoned) as PM.process does:
-    the derived bound of tests/test_gpu_psola.py holds for this arithmetic unchanged, since D enters the addresses only."""
+    the derived bound of tests/test_gpu_psola.py holds for this arithmetic unchanged, since D enters the addresses only.  subnormal="derived" replaces
+    the last term of tol, 2^-149 (1 + (G + 67) / D), by 2^-150 ((Z + G) / D + 2), Z = sum |h_g| (64 / |d_g| + 1) over the fractional grains, and returns
+    (y, tol, poisoned, G, den): PM.process derives it (every rounding in the subnormal range is within 2^-150 absolute; 64 fused multiply-adds and a division
+    per fractional grain, G fused multiply-adds into the numerator, the final division, one unit for the second order).  The default stays bit for bit."""
     x = np.asarray(x, np.float32)
     if x.ndim == 1:
         x = x[None, :]
@@ -140,6 +143,7 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
 
     num = np.zeros((nch, nout)); den = np.zeros(nout)
     A = np.zeros((nch, nout)); S = np.zeros(nout); E = np.zeros((nch, nout)); G = np.zeros(nout, np.int64)
+    Z = np.zeros(nout)                                                    # sum |h_g| (64 / |d_g| + 1) over the fractional grains
     poisoned = np.zeros((nch, nout), bool)
     u = 2.0 ** -24
     i = np.arange(TAPS, dtype=np.int64)
@@ -170,6 +174,8 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
         A[:, sl] += m * np.abs(xt)
         S[sl] += m
         E[:, sl] += np.abs(h) * e
+        if phi != 0:
+            Z[sl] += np.abs(h) * (TAPS / abs(Dg) + 1.0)
         G[sl] += 1
         poisoned[:, sl] |= hit
     cov = G > 0
@@ -179,9 +185,14 @@ def process(x, grains, out_first=0, nout=None, ptable=None, htable=None, bound=F
         return y
     tol = np.zeros((nch, nout))
     Gc = (G[cov] + 3).astype(np.float64)
-    tol[:, cov] = ((u * Gc * (A[:, cov] + np.abs(y[:, cov]) * S[cov]) + E[:, cov]) / den[cov] + u * np.abs(y[:, cov])) * (1.0 + 2.0 ** -10) \
-        + 2.0 ** -149 * (1.0 + (Gc + TAPS) / den[cov])
-    return y, tol, poisoned
+    rel = ((u * Gc * (A[:, cov] + np.abs(y[:, cov]) * S[cov]) + E[:, cov]) / den[cov] + u * np.abs(y[:, cov])) * (1.0 + 2.0 ** -10)
+    if subnormal is None:
+        tol[:, cov] = rel + 2.0 ** -149 * (1.0 + (Gc + TAPS) / den[cov])
+        return y, tol, poisoned
+    if subnormal != "derived":
+        raise ValueError("subnormal: None or 'derived'")
+    tol[:, cov] = rel + 2.0 ** -150 * ((Z[cov] + G[cov]) / den[cov] + 2.0)
+    return y, tol, poisoned, G, den
 
 
 # ---- the planner ------------------------------------------------------------------------------------------------------------------------------

@@ -54,7 +54,8 @@ typedef struct pv_handle pv_handle;
  *     pv_link_channels (an unlinked handle behaves as before); phase resets and onset strength, pv_transient_process / _device,
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
- *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*. */
+ *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
+ *     pv_harmony_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -867,6 +868,68 @@ PV_API int pv_tsm_process_device(pv_tsm *h, const float *d_in, int64_t nin, int6
  * centre would reach 2^30 (grains before it may have been written). */
 PV_API int64_t pv_tsm_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
                            const double *rates, const int32_t *epochs, int32_t *grains, int64_t capacity, int64_t *output_len);
+
+/* ---- harmony voices on the overlap-add path: several differently shifted copies of the voice summed into one output (a separate handle) ---- */
+/* A harmonizer: a third and a fifth above the lead, in key, on the same time base.  A call has nvoices voices, 1 <= nvoices <= 8.  Voice v is a far-grain
+ * table of pv_tsm_process, in its notation and under its rules word for word, and y_v[n] is exactly what pv_tsm_process gives for that table alone: one
+ * num / den per voice (a merged table would normalise over all the grains that cover an output and average the voices instead of adding them).
+ * gains[v nch + c] is a finite float per (voice, channel).  For channel c and output n: acc = 0.0f, and for v ascending, voice v is skipped when
+ * gains[v nch + c] == 0 or no grain of voice v covers n with a non-zero weight (a skipped voice touches nothing: a NaN under the taps of a muted voice
+ * stays out); else acc = acc + f32(gains[v nch + c] * y_v[n]), the product rounded to f32 on its own, then a plain add.  out[c][n] = acc, 0 where no voice
+ * contributes.  So float32 arithmetic on the per-voice outputs of pv_tsm_process reproduces the mix bit for bit.  The order of every sum is a function of
+ * (v, g, i) alone: any partition of the output range into calls gives the same bits.
+ * grains is the concatenation of the voices' tables and voice_first[0 .. nvoices] gives the offsets in grains (records of four int32):
+ * voice_first[0] == 0, non-decreasing, voice_first[nvoices] the number of grains; an empty voice is legal.  Centres are non-decreasing within a voice and
+ * may restart at a voice boundary.
+ * What a call may read: a tile's input is staged once for all voices, so the HULL over the voices of pv_tsm_process's per-voice source range of the tile
+ * (voices with no grain on the tile left out) must not be more than span(max_period, max_rate) of pv_tsm_config; a call with a tile beyond it is
+ * refused, even when every voice alone would fit.  Voices planned by pv_tsm_plan on one row of rates within [1 / max_rate, max_rate] keep to it
+ * (DESIGN.md "Harmony voices").  pv_harmony_create returns PV_ERR_UNSUPPORTED where pv_tsm_create does.
+ * Limits: for a monophonic voice; one row of rates for all voices; in unvoiced stretches every voice is the same unshifted copy, so consonants add up
+ * nvoices-fold: the gains are the remedy. */
+typedef struct pv_harmony_config {
+    int32_t struct_size;     /* sizeof(pv_harmony_config) as the caller compiled it (PV_HARMONY_CONFIG_INIT sets it)              */
+    int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096                                             */
+    int32_t max_rate;        /* 1 .. 4: sizes the span, as pv_tsm_config                                                         */
+    int32_t max_voices;      /* voices per call, 1 .. 8 (0 => 8)                                                                 */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_harmony_config;
+#define PV_HARMONY_CONFIG_INIT { (int32_t)sizeof(pv_harmony_config), 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_harmony pv_harmony;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_harmony_last_error(NULL). */
+PV_API int pv_harmony_create(const pv_harmony_config *cfg, pv_harmony **out);
+PV_API int pv_harmony_destroy(pv_harmony *h);
+PV_API const char *pv_harmony_last_error(const pv_harmony *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_harmony_set_stream(pv_harmony *h, void *hip_stream);
+PV_API int pv_harmony_synchronize(pv_harmony *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1, as pv_tsm_process.  grains, voice_first and gains are HOST tables.  Stateless.  Rejected
+ * with PV_ERR_ARGUMENT before any device work and with the output untouched: everything pv_tsm_process rejects, per voice (the message names voice and
+ * grain, the grain counted within its voice), a malformed voice_first, nvoices < 1, a gain that is not finite, and a tile whose hull exceeds the span
+ * (the message names the tile and the first grain of its lowest voice).  nvoices > max_voices or nch > max_channels: PV_ERR_CAPACITY.  Host pointers,
+ * synchronous, staged in pieces of whole tiles as pv_tsm_process: a piece stages the hull of its tiles cut to the input. */
+PV_API int pv_harmony_process(pv_harmony *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, const int64_t *voice_first,
+                              int32_t nvoices, const float *gains, float *out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains, voice_first and gains stay host tables), asynchronous on the handle's stream. */
+PV_API int pv_harmony_process_device(pv_harmony *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains,
+                                     const int64_t *voice_first, int32_t nvoices, const float *gains, float *d_out, int64_t out_first, int64_t nout,
+                                     int64_t out_stride);
+/* Pure host code: one pitch ratio per (voice, f0 record), voice v a number of scale degrees away from the corrected lead.  r_j is pv_psola_ratios's
+ * one-pole value, exactly, computed once for all voices.  For a voiced record take n, the allowed notes lo and hi on either side of it and the nearest
+ * one ns as pv_psola_ratios does; voice v with k = degrees[v] moves from ns by |k| ALLOWED notes (those whose pitch class has its bit in scale_mask), up
+ * for k > 0, down for k < 0, and i is that whole number of semitones; i = 0 for k = 0 and for unvoiced or empty records.
+ * ratios[v capacity + j] = 2^(r_j + i / 12) held within [1/2, 2], for j < min(nrec, capacity).  So the correction glides with retune and the interval
+ * jumps with the note; on the chromatic mask a degree is a semitone, on a seven-note mask degree 2 is a diatonic third; with k = 0 the row is
+ * pv_psola_ratios's bit for bit.  The clamp limits a voice to an octave either way: a full octave on top of a correction in the same direction saturates.
+ * Returns nrec (the two-call sizing of pv_psola_ratios, `capacity` being the length of a row); -PV_ERR_ARGUMENT for whatever pv_psola_ratios rejects,
+ * nvoices outside [1, 8], a null degrees and |degrees[v]| > 24. */
+PV_API int64_t pv_harmony_ratios(const pv_tune_params *p, const int32_t *records, int64_t nrec, const int32_t *degrees, int32_t nvoices, double *ratios,
+                                 int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ EXPORTS = [
     "pv_epoch_create", "pv_epoch_destroy", "pv_epoch_last_error", "pv_epoch_set_stream", "pv_epoch_synchronize", "pv_epoch_track", "pv_epoch_track_device",
     "pv_epoch_periods", "pv_epoch_plan",
     "pv_tsm_create", "pv_tsm_destroy", "pv_tsm_last_error", "pv_tsm_set_stream", "pv_tsm_synchronize", "pv_tsm_process", "pv_tsm_process_device", "pv_tsm_plan",
+    "pv_harmony_create", "pv_harmony_destroy", "pv_harmony_last_error", "pv_harmony_set_stream", "pv_harmony_synchronize", "pv_harmony_process",
+    "pv_harmony_process_device", "pv_harmony_ratios",
 ]
 
 
@@ -107,6 +109,15 @@ class _EpochParams(C.Structure):
 
 class _TsmConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+class _HarmonyConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_voices", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+def make_harmony_config(max_period, max_rate=1, max_voices=0, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_harmony_config with struct_size filled in (the C side's PV_HARMONY_CONFIG_INIT)."""
+    return _HarmonyConfig(C.sizeof(_HarmonyConfig), max_period, max_rate, max_voices, max_channels, max_outputs, device_id, flags)
 
 
 def make_tsm_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
@@ -371,6 +382,16 @@ def load_library():
                               C.POINTER(C.c_int64)]
     L.pv_tsm_last_error.restype = C.c_char_p
     L.pv_tsm_plan.restype = C.c_int64
+    L.pv_harmony_create.argtypes = [C.POINTER(_HarmonyConfig), C.POINTER(vp)]
+    L.pv_harmony_destroy.argtypes = [vp]
+    L.pv_harmony_last_error.argtypes = [vp]
+    L.pv_harmony_set_stream.argtypes = [vp, vp]
+    L.pv_harmony_synchronize.argtypes = [vp]
+    L.pv_harmony_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.POINTER(C.c_int64), C.c_int32, fp, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_harmony_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.POINTER(C.c_int64), C.c_int32, fp, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_harmony_ratios.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, ip, C.c_int32, C.POINTER(C.c_double), C.c_int64]
+    L.pv_harmony_last_error.restype = C.c_char_p
+    L.pv_harmony_ratios.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1678,3 +1699,120 @@ class Tsm(_Handle):
                                       self.max_period, ratios=ratios, rates=rates, epochs=found)
         y = self.process(x, grains, 0, output_len)
         return (y[0] if one else y), grains
+
+
+def harmony_ratios(records, sample_rate, degrees, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0):
+    """pv_harmony_ratios: float64[nvoices, nrec], one pitch ratio within [1/2, 2] per (voice, f0 record of ONE channel).  Voice v lies degrees[v] ALLOWED
+    notes of scale_mask above (below, when negative) the note the lead is corrected onto: on the chromatic mask a degree is a semitone, on a seven-note
+    mask degree 2 is a diatonic third.  The row of degree 0 is tune_ratios's bit for bit; unvoiced records give every voice the lead's ratio.  1 to 8
+    voices, |degree| <= 24; a full octave on top of a correction in the same direction saturates at the clamp."""
+    L = load_library()
+    r, nrec = _one_channel_records(records)
+    deg = np.ascontiguousarray(degrees, dtype=np.int32)
+    if deg.ndim != 1:
+        raise ValueError("degrees must be int32[nvoices]")
+    p = make_tune_params(0, 0, float(sample_rate), 0, 0, 0, 0, scale_mask, float(strength), float(retune), float(a4), 0)
+    out = np.zeros((deg.size, nrec), np.float64)
+    ip = C.POINTER(C.c_int32)
+    n = L.pv_harmony_ratios(C.byref(p), r.ctypes.data_as(ip) if nrec else None, nrec, deg.ctypes.data_as(ip) if deg.size else None, deg.size,
+                            out.ctypes.data_as(C.POINTER(C.c_double)) if out.size else None, nrec)
+    if n < 0:
+        raise ValueError("harmony_ratios: bad argument (tune_ratios's ranges, 1 to 8 voices, degrees within [-24, 24])")
+    return out
+
+
+class Harmony(_Handle):
+    """Harmony voices on the overlap-add path (pv_harmony_*): several differently shifted copies of a monophonic voice summed into one output by one
+    kernel.  Every voice is a far-grain table of Tsm.process and gives exactly Tsm.process's output for that table; out[c] is the float32 sum over the
+    voices, in order, of gains[v, c] * y_v (the product rounded on its own), skipping a voice where its gain is 0 or no grain of it covers the output.  A
+    tile of 1024 outputs stages its input once for all voices: the hull of what the voices read there must fit Tsm's span of (max_period, max_rate).
+    Stateless; any partition of the output range gives the same bits.  Limits: a monophonic voice; one row of rates for all voices; in unvoiced
+    stretches every voice is the same unshifted copy, so consonants add up V-fold (the gains are the remedy)."""
+
+    _prefix = "pv_harmony"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_voices=8, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_harmony_config(max_period, max_rate, max_voices, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_voices, self.max_channels = max_period, max_rate, max_voices, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    @staticmethod
+    def _tables(tables, gains, nch):
+        """(concatenated grains int32[ngrains, 4], voice_first int64[V + 1], gains float32[V, nch]) of a list of far-grain arrays and gains [V] or [V, nch]."""
+        parts = [Psola._grains(t)[0].reshape(-1, 4) for t in tables]
+        nv = len(parts)
+        first = np.zeros(nv + 1, np.int64)
+        if nv:
+            first[1:] = np.cumsum([q.shape[0] for q in parts])
+        g = np.ascontiguousarray(np.concatenate(parts, axis=0) if nv else np.zeros((0, 4)), dtype=np.int32)
+        w = np.asarray(gains, dtype=np.float32)
+        if w.ndim == 1:
+            w = np.repeat(w[:, None], nch, axis=1)
+        if w.shape != (nv, nch):
+            raise ValueError("gains must have the shape [V] or [V, nch]")
+        return g, first, np.ascontiguousarray(w)
+
+    def process(self, x, tables, gains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), tables: a list of far-grain arrays int32[., 4], one per voice, gains: [V] or [V, nch] -> float32[nch, nout], outputs
+        out_first .. out_first + nout - 1 (default: n - out_first; pass tsm_plan's output_len for a whole stretched signal)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        g, first, w = self._tables(tables, gains, nch)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_harmony_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if g.size else None,
+                                               first.ctypes.data_as(C.POINTER(C.c_int64)), len(first) - 1, _fp(w), _fp(y), int(out_first), nout, max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, tables, gains, d_out, out_first, nout, out_stride):
+        """pv_harmony_process_device on raw device pointers (ints), asynchronous on the handle's stream; tables and gains are host tables."""
+        g, first, w = self._tables(tables, gains, nch)
+        self._check(self._L.pv_harmony_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if g.size else None,
+                                                      first.ctypes.data_as(C.POINTER(C.c_int64)), len(first) - 1, _fp(w), C.c_void_p(d_out), out_first, nout,
+                                                      out_stride))
+
+    def process_tuned(self, x, sample_rate, degrees=(0, 2, 4), gains=None, rate=1.0, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458,
+                      a4=440.0, epochs=False):
+        """Offline harmonizer of a monophonic voice: one F0Tracker.track (channel 0: one plan for all channels), optionally one epoch track,
+        harmony_ratios, one tsm_plan per voice, all on the same row of rates, and one kernel call.  degrees: one per voice, see harmony_ratios; gains: [V]
+        or [V, nch], default 1 / V each; rate, tracker and epochs as Tsm.process_tuned.  x: float32[nch, n] (host).  Returns (y float32[nch,
+        output_len], tables): output_len is voice 0's."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nv = len(degrees)
+        own = tracker is None
+        if own:
+            max_lag = max(self.max_period, 3)
+            tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
+        try:
+            records = tracker.track(x[0], threshold)[0]
+        finally:
+            if own:
+                tracker.close()
+        nrec = records.shape[0]
+        ratios = harmony_ratios(records, sample_rate, degrees, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+        rates = np.full(nrec, float(rate)) if np.ndim(rate) == 0 else np.ascontiguousarray(rate, dtype=np.float64)
+        if rates.shape != (nrec,):
+            raise ValueError(f"rate must be one number or one per f0 record ({nrec})")
+        min_period = tracker.min_lag
+        found = None
+        if epochs:
+            longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
+            marks = EpochTracker(2 * longest, tracker.hop, longest)
+            try:
+                found = marks.track(x[0], epoch_periods(records))[0]
+            finally:
+                marks.close()
+        plans = [tsm_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                          self.max_period, ratios=ratios[v], rates=rates, epochs=found) for v in range(nv)]
+        tables = [g for g, _ in plans]
+        y = self.process(x, tables, np.full(nv, 1.0 / nv, np.float32) if gains is None else gains, 0, plans[0][1])
+        return (y[0] if one else y), tables

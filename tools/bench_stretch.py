@@ -24,8 +24,11 @@ channel of a pulse train of period 217.3; frames/s counts channel-frames.
 With --tsm: only the time-scale modification kernel (pv_tsm_process_device, max_period 1024, max_rate 2) on the --psola workload: 2^24 outputs mono,
 periods 192 .. 208 moved by 1.25, at the rates 1, 1/2 and 2 (the input is rate times as long as the output); the --psola line runs first in the same
 process: at rate 1 the two kernels do the same arithmetic on the same table.
+With --harmony: only the harmony kernel (pv_harmony_process_device, max_period 1024, max_rate 2) on the --psola workload: 2^24 outputs mono, V = 4 voices
+at the degrees (0, 2, 4, -3) of C major, gains 1/4, one grain table per voice from tsm_plan at rate 1; then what stands in for it without the kernel:
+four pv_tsm_process_device calls into four buffers and a torch weighted sum.  Both lines are input-resident and use the same steps and warmup.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony]
 """
 import argparse
 import json
@@ -258,6 +261,50 @@ def tsm_line(torch, phaze_amd, n, ratio, rate, steps, warmup):
             "hbm_fraction": (nin + nout) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def harmony_lines(torch, phaze_amd, n, steps, warmup):
+    hop = 256
+    nrec = n // hop
+    lag = 200 + (np.arange(nrec) // 64) % 17 - 8                       # psola_line's records
+    records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+    degrees = (0, 2, 4, -3)
+    nv = len(degrees)
+    ratios = phaze_amd.harmony_ratios(records, 48000.0, degrees, scale_mask=0xAB5)
+    plans = [phaze_amd.tsm_plan(records, hop, hop // 2, n, 256.0, 32, 1024, ratios[v], np.ones(nrec)) for v in range(nv)]
+    tables, nout = [g for g, _ in plans], plans[0][1]
+    gains = np.full(nv, 1.0 / nv, np.float32)
+    x = (torch.rand((1, n), device="cuda") - 0.5).contiguous()
+    y = torch.empty((1, nout), device="cuda")
+    stream = torch.cuda.Stream()
+    hv = phaze_amd.Harmony(1024, 2, max_voices=nv, max_channels=1, max_outputs=1024)
+    hv.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: hv.process_device(x.data_ptr(), n, n, 1, tables, gains, y.data_ptr(), 0, nout, nout), steps, warmup)
+    hv.close()
+    common = {"max_period": 1024, "max_rate": 2, "voices": nv, "degrees": list(degrees), "channels": 1, "inputs": n, "outputs": nout,
+              "grains": [int(g.shape[0]) for g in tables]}
+    fused = dict(common, kernel="pv_harmony", ms_per_launch=round(ms, 4), outputs_per_s=nout / (ms * 1e-3), hbm_fraction=(n + nout) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S)
+    # the same result without the kernel: one pv_tsm launch per voice into its own buffer, then a weighted sum
+    ts = phaze_amd.Tsm(1024, 2, max_channels=1, max_outputs=1024)
+    ts.set_stream(stream.cuda_stream)
+    parts = torch.empty((nv, nout), device="cuda")
+    w = torch.from_numpy(gains).cuda()
+    z = torch.empty((1, nout), device="cuda")
+    torch.cuda.synchronize()
+
+    def separate():
+        for v in range(nv):
+            ts.process_device(x.data_ptr(), n, n, 1, tables[v], parts[v].data_ptr(), 0, nout, nout)
+        torch.matmul(w[None, :], parts, out=z)
+
+    ms2 = _time(torch, stream, separate, steps, warmup)
+    ts.close()
+    same = float((z - y).abs().max().item())
+    apart = dict(common, kernel="pv_tsm x 4 + torch weighted sum", ms_per_launch=round(ms2, 4), outputs_per_s=nout / (ms2 * 1e-3),
+                 hbm_fraction=(nv * n + (2 * nv + 1) * nout) * 4 / (ms2 * 1e-3) / HBM_BYTES_PER_S, max_abs_difference_to_fused=same,
+                 fused_speedup=round(ms2 / ms, 4))
+    return fused, apart
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -291,9 +338,14 @@ def main():
     ap.add_argument("--psola-outputs", type=int, default=1 << 24, help="outputs of the overlap-add line")
     ap.add_argument("--epoch", action="store_true", help="only the epoch kernel lines (--f0-frames frames per channel)")
     ap.add_argument("--tsm", action="store_true", help="only the overlap-add line and the time-scale modification lines at the rates 1, 1/2 and 2 (--psola-outputs outputs)")
+    ap.add_argument("--harmony", action="store_true", help="only the harmony line (four voices, --psola-outputs outputs) and the four launches plus mix it replaces")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.harmony:
+        for line in harmony_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
+            print(json.dumps(line), flush=True)
+        return
     if args.psola:
         print(json.dumps(psola_line(torch, phaze_amd, args.psola_outputs, 1.25, args.steps, args.warmup)), flush=True)
         return

@@ -55,7 +55,7 @@ typedef struct pv_handle pv_handle;
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
  *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
- *     pv_harmony_*. */
+ *     pv_harmony_*; its per-take plans, pv_takes_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -930,6 +930,67 @@ PV_API int pv_harmony_process_device(pv_harmony *h, const float *d_in, int64_t n
  * nvoices outside [1, 8], a null degrees and |degrees[v]| > 24. */
 PV_API int64_t pv_harmony_ratios(const pv_tune_params *p, const int32_t *records, int64_t nrec, const int32_t *degrees, int32_t nvoices, double *ratios,
                                  int64_t capacity);
+
+/* ---- per-take plans on the overlap-add path: one call plays K independently planned takes of different lengths (a separate handle) ---- */
+/* A take is one monophonic recording with its own plan: its own input, far-grain table, length and output range.  (It is not a voice of pv_harmony,
+ * a differently shifted copy of one input, and not a channel, a row that shares a plan.)  For every take k, channel c and n in
+ * [out_first, out_first + nout), out[c * out_stride + n - out_first] is exactly what
+ *     pv_tsm_process(h', in, nin, in_stride, nch, grains, ngrains, out, out_first, nout, out_stride)
+ * writes for the take alone, h' a pv_tsm handle of the same (max_period, max_rate): the same bits.  Tiles of 1024 count from each take's own out_first,
+ * and the span rule, and so which takes are refused, is pv_tsm_process's per take.  The order of every sum is a function of (g, i) alone: a take given as
+ * two takes [0, a) and [a, n) that share `in` and write adjacent outputs gives the bits of one.  Takes may share an input (two plans on one recording:
+ * a double-track); no two output rows of a call may overlap.  nch is common to the call.
+ * The tiles of all takes go out in at most four launches, grouped by how many workgroups of their source range fit the LDS of a compute unit, so that
+ * one take at a high rate does not lower the occupancy of the others (DESIGN.md "Takes"). */
+typedef struct pv_take {
+    const float   *in;          /* channel c at in + c*in_stride, nin samples (host or device, as the entry point says)              */
+    int64_t        nin, in_stride;
+    const int32_t *grains;      /* this take's far grains {t, w, D, L}, HOST, pv_tsm_process's rules word for word                   */
+    int64_t        ngrains;
+    float         *out;         /* channel c at out + c*out_stride; out[0] is output out_first                                       */
+    int64_t        out_first, nout, out_stride;
+} pv_take;
+
+typedef struct pv_takes_config {
+    int32_t struct_size;     /* sizeof(pv_takes_config) as the caller compiled it (PV_TAKES_CONFIG_INIT sets it)                  */
+    int32_t max_period;      /* the largest half length L a take may pass, 2 .. 4096                                             */
+    int32_t max_rate;        /* 1 .. 4: sizes the span, as pv_tsm_config                                                         */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_takes_config;
+#define PV_TAKES_CONFIG_INIT { (int32_t)sizeof(pv_takes_config), 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_takes pv_takes;
+
+/* Config errors are returned before any device is touched, PV_ERR_UNSUPPORTED where pv_tsm_create returns it; failures are readable through
+ * pv_takes_last_error(NULL).  There is no limit on the takes of a call to configure: the per-take device records grow on demand. */
+PV_API int pv_takes_create(const pv_takes_config *cfg, pv_takes **out);
+PV_API int pv_takes_destroy(pv_takes *h);
+PV_API const char *pv_takes_last_error(const pv_takes *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_takes_set_stream(pv_takes *h, void *hip_stream);
+PV_API int pv_takes_synchronize(pv_takes *h);
+/* ntakes takes of nch channels each, HOST in / out pointers, synchronous.  Everything is validated for all takes before any device work, and a refused
+ * call leaves every take's output untouched.  PV_ERR_ARGUMENT: everything pv_tsm_process rejects, per take (the message names the take and the grain,
+ * the grain counted within its take); ntakes < 0 or > 65536; a null takes with ntakes > 0; outputs that together reach 2^30 or more than 2^27 grains
+ * together; two output rows, over all takes and channels, that overlap (the message names both takes).  nch > max_channels: PV_ERR_CAPACITY.
+ * ntakes == 0, nch == 0 or every nout == 0: PV_OK, nothing queued.  A take with nout == 0 or ngrains == 0 is legal; outputs no grain covers are +0.
+ * Staged in pieces: a piece is a run of consecutive tiles in take order with at most max_outputs outputs, and stages per take the input range its
+ * tiles read. */
+PV_API int pv_takes_process(pv_takes *h, const pv_take *takes, int32_t ntakes, int32_t nch);
+/* The same with DEVICE in / out pointers in every take (takes and grains stay host tables), asynchronous on the handle's stream: one table upload and at
+ * most four launches. */
+PV_API int pv_takes_process_device(pv_takes *h, const pv_take *takes, int32_t ntakes, int32_t nch);
+/* Pure host code: the tile walk the process calls run on.  cfg is validated as pv_takes_create validates it and used for max_period and max_rate only;
+ * the takes are validated as the process calls validate them, except that in and out are never looked at and the overlap check is left out.  Per tile,
+ * in take order and within a take in tile order, eight int32 {take, first, g_first, g_end, src0, src_count, cls, 0}: first is the tile's first output
+ * relative to the take's out_first, g_first and g_end count within the take's own table, src0 and src_count are pv_tsm_process's source range of the
+ * tile, and cls = min of 4 and 163840 div the LDS bytes of a launch that stages s samples, s = max of 128 and src_count rounded up to 64, is the
+ * tile's occupancy class, always 1 .. 4: where the rounded s would not fit the LDS at all, s is src_count itself and cls is 1.  Returns the number of tiles and writes at most `capacity` of them; -PV_ERR_* on failure, with the message in
+ * pv_takes_last_error(NULL): nothing is written then, except that the records before a tile beyond the span may have been. */
+PV_API int64_t pv_takes_tiles(const pv_takes_config *cfg, const pv_take *takes, int32_t ntakes, int32_t *tiles, int64_t capacity);
 
 #ifdef __cplusplus
 }

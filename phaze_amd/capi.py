@@ -47,6 +47,8 @@ EXPORTS = [
     "pv_tsm_create", "pv_tsm_destroy", "pv_tsm_last_error", "pv_tsm_set_stream", "pv_tsm_synchronize", "pv_tsm_process", "pv_tsm_process_device", "pv_tsm_plan",
     "pv_harmony_create", "pv_harmony_destroy", "pv_harmony_last_error", "pv_harmony_set_stream", "pv_harmony_synchronize", "pv_harmony_process",
     "pv_harmony_process_device", "pv_harmony_ratios",
+    "pv_takes_create", "pv_takes_destroy", "pv_takes_last_error", "pv_takes_set_stream", "pv_takes_synchronize", "pv_takes_process", "pv_takes_process_device",
+    "pv_takes_tiles",
 ]
 
 
@@ -113,6 +115,21 @@ class _TsmConfig(C.Structure):
 
 class _HarmonyConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_voices", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+class _TakesConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+class _Take(C.Structure):
+    """pv_take: in and out are addresses (host or device, as the entry point says)."""
+    _fields_ = [("in_", C.c_void_p), ("nin", C.c_int64), ("in_stride", C.c_int64), ("grains", C.POINTER(C.c_int32)), ("ngrains", C.c_int64), ("out", C.c_void_p),
+                ("out_first", C.c_int64), ("nout", C.c_int64), ("out_stride", C.c_int64)]
+
+
+def make_takes_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_takes_config with struct_size filled in (the C side's PV_TAKES_CONFIG_INIT)."""
+    return _TakesConfig(C.sizeof(_TakesConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
 
 
 def make_harmony_config(max_period, max_rate=1, max_voices=0, max_channels=1, max_outputs=0, device_id=0, flags=0):
@@ -392,6 +409,16 @@ def load_library():
     L.pv_harmony_ratios.argtypes = [C.POINTER(_TuneParams), ip, C.c_int64, ip, C.c_int32, C.POINTER(C.c_double), C.c_int64]
     L.pv_harmony_last_error.restype = C.c_char_p
     L.pv_harmony_ratios.restype = C.c_int64
+    L.pv_takes_create.argtypes = [C.POINTER(_TakesConfig), C.POINTER(vp)]
+    L.pv_takes_destroy.argtypes = [vp]
+    L.pv_takes_last_error.argtypes = [vp]
+    L.pv_takes_set_stream.argtypes = [vp, vp]
+    L.pv_takes_synchronize.argtypes = [vp]
+    L.pv_takes_process.argtypes = [vp, C.POINTER(_Take), C.c_int32, C.c_int32]
+    L.pv_takes_process_device.argtypes = [vp, C.POINTER(_Take), C.c_int32, C.c_int32]
+    L.pv_takes_tiles.argtypes = [C.POINTER(_TakesConfig), C.POINTER(_Take), C.c_int32, ip, C.c_int64]
+    L.pv_takes_last_error.restype = C.c_char_p
+    L.pv_takes_tiles.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1816,3 +1843,132 @@ class Harmony(_Handle):
         tables = [g for g, _ in plans]
         y = self.process(x, tables, np.full(nv, 1.0 / nv, np.float32) if gains is None else gains, 0, plans[0][1])
         return (y[0] if one else y), tables
+
+
+def _take_array(entries):
+    """(pv_take array, the arrays it points into) of entries (in address, nin, in_stride, grains, out address, out_first, nout, out_stride)."""
+    arr = (_Take * max(len(entries), 1))()
+    keep = []
+    for k, (d_in, nin, in_stride, grains, d_out, out_first, nout, out_stride) in enumerate(entries):
+        g, ng = Psola._grains(grains)
+        keep.append(g)
+        arr[k] = _Take(d_in or None, int(nin), int(in_stride), g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng, d_out or None, int(out_first), int(nout),
+                       int(out_stride))
+    return arr, keep
+
+
+def takes_tiles(max_period, max_rate, tables, out_firsts, nouts):
+    """pv_takes_tiles: int32[ntiles, 8] = {take, first, g_first, g_end, src0, src_count, cls, 0} per tile of 1024 outputs of a Takes call, in (take, tile)
+    order: the host's tile walk, pure host code.  tables: one far-grain array per take; out_firsts, nouts: one number per take.  Raises PvError for
+    whatever Takes.process refuses in the config, the tables and the ranges."""
+    L = load_library()
+    if not len(tables) == len(out_firsts) == len(nouts):
+        raise ValueError("tables, out_firsts and nouts must have one entry per take")
+    arr, keep = _take_array([(0, 0, 0, g, 0, f, n, 0) for g, f, n in zip(tables, out_firsts, nouts)])
+    cfg = make_takes_config(int(max_period), int(max_rate))
+    n = L.pv_takes_tiles(C.byref(cfg), arr, len(tables), None, 0)
+    if n < 0:
+        raise PvError(int(-n), L.pv_takes_last_error(None).decode())
+    out = np.zeros((n, 8), np.int32)
+    if n:
+        L.pv_takes_tiles(C.byref(cfg), arr, len(tables), out.ctypes.data_as(C.POINTER(C.c_int32)), n)
+    return out
+
+
+class Takes(_Handle):
+    """Per-take plans on the overlap-add path (pv_takes_*): one call plays K independently planned takes of different lengths.  A take is one monophonic
+    recording with its own input, far-grain table, length and output range; take k's output is exactly Tsm.process on take k alone, bit for bit, on a
+    Tsm of the same (max_period, max_rate).  Takes may share an input; no two output rows may overlap; the channel count is common to the call.  The
+    tiles of all takes go out in at most four launches, grouped by occupancy class (takes_tiles).  Stateless."""
+
+    _prefix = "pv_takes"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_takes_config(max_period, max_rate, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_channels = max_period, max_rate, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    def process(self, xs, tables, out_first=None, nouts=None):
+        """xs: a list of float32[n_k] or float32[nch, n_k] (host), the same nch for all; tables: one far-grain array int32[., 4] per take; out_first, nouts: one
+        number per take (default: 0, and n_k - out_first_k) -> a list of float32 arrays, [nout_k] for a one-dimensional take, else [nch, nout_k]."""
+        K = len(xs)
+        if len(tables) != K or (out_first is not None and len(out_first) != K) or (nouts is not None and len(nouts) != K):
+            raise ValueError("xs, tables, out_first and nouts must have one entry per take")
+        xs = [np.ascontiguousarray(x, dtype=np.float32) for x in xs]
+        one = [x.ndim == 1 for x in xs]
+        rows = [x[None, :] if x.ndim == 1 else x for x in xs]
+        if any(x.ndim != 2 for x in rows) or len({x.shape[0] for x in rows}) > 1:
+            raise ValueError("every take must be float32[n] or float32[nch, n] with the same nch")
+        nch = rows[0].shape[0] if K else 0
+        firsts = [0] * K if out_first is None else [int(v) for v in out_first]
+        counts = [x.shape[1] - f for x, f in zip(rows, firsts)] if nouts is None else [int(v) for v in nouts]
+        ys = [np.zeros((nch, max(n, 0)), np.float32) for n in counts]
+        arr, keep = _take_array([(x.ctypes.data, x.shape[1], x.shape[1], g, y.ctypes.data, f, n, max(n, 0)) for x, g, y, f, n in zip(rows, tables, ys, firsts, counts)])
+        self._check(self._L.pv_takes_process(self._h, arr, K, nch))
+        return [y[0] if o else y for y, o in zip(ys, one)]
+
+    def process_device(self, takes, nch):
+        """pv_takes_process_device: takes is a list of (d_in, nin, in_stride, grains, d_out, out_first, nout, out_stride) with raw device pointers (ints) and a
+        host far-grain array each; asynchronous on the handle's stream."""
+        arr, keep = _take_array(takes)
+        self._check(self._L.pv_takes_process_device(self._h, arr, len(takes), int(nch)))
+
+    def process_tuned(self, xs, sample_rate, rate=1.0, scale_mask=0xFFF, strength=1.0, retune=1.0, threshold=2458, a4=440.0, epochs=False):
+        """Offline tempo change and pitch correction of K takes in one overlap-add call: what Tsm.process_tuned does for one.  Channel 0 of every take is
+        zero-padded to the longest take and all are tracked in ONE F0Tracker.track call of K channels (in chunks, if K is more than the tracker takes);
+        take k keeps the first frames(n_k) records of its row, which are the records of tracking take k alone, a record being an exact integer function
+        of its own frame.  Then tune_ratios and tsm_plan per take on the host, and one Takes.process.  rate: one number, or one entry per take, each a
+        number or a row float64[nrec_k].  epochs=True: the epoch tracker runs once PER TAKE, since it takes one row of periods for all its channels.
+        The tracker is Tsm.process_tuned's default one (window 1024, hop 256, lags up to max_period) with K channels, so there is no tracker argument.
+        A take shorter than window + max_lag samples has no whole f0 frame: it gets no records and tsm_plan's unvoiced grains, exactly as
+        Tsm.process_tuned treats it alone.  xs: a list of float32[n_k] or float32[nch, n_k] (host).  Returns (ys, tables): ys[k] has tsm_plan's
+        output_len of take k."""
+        K = len(xs)
+        xs = [np.ascontiguousarray(x, dtype=np.float32) for x in xs]
+        leads = [x if x.ndim == 1 else x[0] for x in xs]
+        rate_of = [rate] * K if isinstance(rate, (int, float, np.integer, np.floating)) else list(rate)       # (a list may mix numbers and rows)
+        if len(rate_of) != K:
+            raise ValueError(f"rate must be one number or one entry per take ({K})")
+        if K == 0:
+            return [], []
+        max_lag = max(self.max_period, 3)
+        window, hop, min_lag = 1024, 256, max(2, min(32, max_lag // 2))
+        longest = max(v.shape[0] for v in leads)
+        chunk = 1024
+        records = []
+        tracker = F0Tracker(window, hop, min_lag, max_lag, max_channels=min(K, chunk))           # one tracker for all chunks
+        try:
+            for k0 in range(0, K, chunk):
+                part = leads[k0:k0 + chunk]
+                padded = np.zeros((len(part), longest), np.float32)
+                for j, v in enumerate(part):
+                    padded[j, :v.shape[0]] = v
+                rows = tracker.track(padded, threshold)
+                records += [np.ascontiguousarray(rows[j, :tracker.frames(v.shape[0])]) for j, v in enumerate(part)]
+        finally:
+            tracker.close()
+        marks = None
+        if epochs:
+            reach = min(max_lag, 2048, (window + max_lag) // 2)
+            marks = EpochTracker(2 * reach, hop, reach)                                          # one handle, one track call per take
+        tables, lengths = [], []
+        try:
+            for k in range(K):
+                rec, n = records[k], leads[k].shape[0]
+                nrec = rec.shape[0]
+                ratios = tune_ratios(rec, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+                rates = np.full(nrec, float(rate_of[k])) if np.ndim(rate_of[k]) == 0 else np.ascontiguousarray(rate_of[k], dtype=np.float64)
+                if rates.shape != (nrec,):
+                    raise ValueError(f"take {k}: rate must be one number or one per f0 record ({nrec})")
+                found = marks.track(leads[k], epoch_periods(rec))[0] if marks is not None else None
+                grains, output_len = tsm_plan(rec, hop, (window + max_lag) // 2, n, float(min(max(256, min_lag), self.max_period)), min_lag, self.max_period,
+                                              ratios=ratios, rates=rates, epochs=found)
+                tables.append(grains)
+                lengths.append(output_len)
+        finally:
+            if marks is not None:
+                marks.close()
+        return self.process(xs, tables, [0] * K, lengths), tables

@@ -27,8 +27,13 @@ process: at rate 1 the two kernels do the same arithmetic on the same table.
 With --harmony: only the harmony kernel (pv_harmony_process_device, max_period 1024, max_rate 2) on the --psola workload: 2^24 outputs mono, V = 4 voices
 at the degrees (0, 2, 4, -3) of C major, gains 1/4, one grain table per voice from tsm_plan at rate 1; then what stands in for it without the kernel:
 four pv_tsm_process_device calls into four buffers and a torch weighted sum.  Both lines are input-resident and use the same steps and warmup.
+With --takes: only the per-take call (pv_takes_process_device, max_period 1024) against the loop it replaces: 256 takes of 2^16 outputs mono (--psola-outputs
+in all), each with its own table, periods 192 .. 208 moved by 1.25; (a) all at rate 1 on a (1024, 2) configuration, (b) every 16th take planned at rate 4
+on (1024, 4): tiles of mixed occupancy classes.  The yardstick is a loop of 256 pv_tsm_process_device calls on one Tsm of the same configuration, then one
+synchronise.  Input-resident; the host's validation, walk and upload are inside the timed call; the outputs are asserted equal before timing; three runs
+of each line, alternating, and their spread.
 
-    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony]
+    python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony] [--takes]
 """
 import argparse
 import json
@@ -305,6 +310,77 @@ def harmony_lines(torch, phaze_amd, n, steps, warmup):
     return fused, apart
 
 
+def takes_lines(torch, phaze_amd, total, ntakes, steps, warmup, runs=3):
+    """Two workloads of `ntakes` takes with `total` outputs together, each take with its own table: (a) all at rate 1 on a (1024, 2) configuration, (b) every
+    16th take planned at rate 4 on (1024, 4), which gives tiles of mixed occupancy classes.  Per workload the batched call (one pv_takes_process_device) and
+    what the library could do without it (a loop of pv_tsm_process_device calls on one Tsm of the same configuration, then one synchronise), `runs` runs of
+    each, alternating.  Both go through the raw C entry points on arguments built beforehand, so that the binding's per-call work is in neither."""
+    import ctypes as C
+    from phaze_amd import capi
+    hop = 256
+    per = total // ntakes
+    lines = []
+    for label, max_rate, fast_every in (("rate 1", 2, 0), ("every 16th take at rate 4", 4, 16)):
+        xs, tables, nins, nouts = [], [], [], []
+        for k in range(ntakes):
+            rate = 4.0 if fast_every and k % fast_every == fast_every - 1 else 1.0
+            nin = int(per * rate)
+            nrec = nin // hop
+            lag = 200 + ((np.arange(nrec) + 5 * k) // 64) % 17 - 8             # psola_line's records, from another place per take
+            records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+            g, nout = phaze_amd.tsm_plan(records, hop, hop // 2, nin, 256.0, 32, 1024, np.full(nrec, 1.25), np.full(nrec, rate))
+            tables.append(np.ascontiguousarray(g))
+            nins.append(nin)
+            nouts.append(nout)
+            xs.append((torch.rand((nin,), device="cuda") - 0.5).contiguous())
+        ys = [torch.zeros((n,), device="cuda") for n in nouts]
+        zs = [torch.zeros((n,), device="cuda") for n in nouts]
+        stream = torch.cuda.Stream()
+        tk = phaze_amd.Takes(1024, max_rate, max_channels=1, max_outputs=1024)
+        ts = phaze_amd.Tsm(1024, max_rate, max_channels=1, max_outputs=1024)
+        tk.set_stream(stream.cuda_stream)
+        ts.set_stream(stream.cuda_stream)
+        ip = C.POINTER(C.c_int32)
+        arr = (capi._Take * ntakes)()
+        for k in range(ntakes):
+            arr[k] = capi._Take(xs[k].data_ptr(), nins[k], nins[k], tables[k].ctypes.data_as(ip), tables[k].shape[0], ys[k].data_ptr(), 0, nouts[k], nouts[k])
+        loop_args = [(C.c_void_p(xs[k].data_ptr()), nins[k], nins[k], 1, tables[k].ctypes.data_as(ip), tables[k].shape[0], C.c_void_p(zs[k].data_ptr()), 0, nouts[k],
+                      nouts[k]) for k in range(ntakes)]
+        L = tk._L
+
+        def batched():
+            tk._check(L.pv_takes_process_device(tk._h, arr, ntakes, 1))
+
+        def loop():
+            for a in loop_args:
+                ts._check(L.pv_tsm_process_device(ts._h, *a))
+
+        torch.cuda.synchronize()
+        batched()
+        loop()
+        tk.synchronize()
+        ts.synchronize()
+        torch.cuda.synchronize()
+        assert all(torch.equal(y, z) for y, z in zip(ys, zs)), "the batched call and the loop disagree"
+        tiles = phaze_amd.takes_tiles(1024, max_rate, tables, [0] * ntakes, nouts)
+        ms = {"batched": [], "loop": []}
+        for _ in range(runs):
+            ms["batched"].append(_time(torch, stream, batched, steps, warmup))
+            ms["loop"].append(_time(torch, stream, loop, steps, warmup))
+        tk.close()
+        ts.close()
+        nout = int(sum(nouts))
+        common = {"workload": label, "max_period": 1024, "max_rate": max_rate, "takes": ntakes, "channels": 1, "inputs": int(sum(nins)), "outputs": nout,
+                  "grains": int(sum(g.shape[0] for g in tables)), "tiles_per_class": [int(np.sum(tiles[:, 6] == c)) for c in (1, 2, 3, 4)], "outputs_equal": True}
+        for kernel, key in (("pv_takes (one call)", "batched"), (f"pv_tsm x {ntakes} (a loop of calls)", "loop")):
+            v = ms[key]
+            best = min(v)
+            lines.append(dict(common, kernel=kernel, ms_per_launch=round(best, 4), ms_per_launch_runs=[round(t, 4) for t in v], spread=round((max(v) - best) / best, 4),
+                              outputs_per_s=nout / (best * 1e-3), hbm_fraction=(sum(nins) + nout) * 4 / (best * 1e-3) / HBM_BYTES_PER_S))
+        lines[-1]["batched_speedup"] = round(min(ms["loop"]) / min(ms["batched"]), 4)
+    return lines
+
+
 def pitch_line(torch, phaze_amd, label, N, hop, nch, T, pitch, steps, warmup):
     x = (torch.rand((nch, T * hop), device="cuda") - 0.5).contiguous()
     y = torch.empty_like(x)
@@ -339,9 +415,14 @@ def main():
     ap.add_argument("--epoch", action="store_true", help="only the epoch kernel lines (--f0-frames frames per channel)")
     ap.add_argument("--tsm", action="store_true", help="only the overlap-add line and the time-scale modification lines at the rates 1, 1/2 and 2 (--psola-outputs outputs)")
     ap.add_argument("--harmony", action="store_true", help="only the harmony line (four voices, --psola-outputs outputs) and the four launches plus mix it replaces")
+    ap.add_argument("--takes", action="store_true", help="only the per-take lines (256 takes, --psola-outputs outputs in all) and the loops of pv_tsm calls they replace")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.takes:
+        for line in takes_lines(torch, phaze_amd, args.psola_outputs, 256, args.steps, args.warmup):
+            print(json.dumps(line), flush=True)
+        return
     if args.harmony:
         for line in harmony_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
             print(json.dumps(line), flush=True)

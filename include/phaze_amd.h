@@ -55,7 +55,7 @@ typedef struct pv_handle pv_handle;
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
  *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
- *     pv_harmony_*; its per-take plans, pv_takes_*. */
+ *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -823,7 +823,8 @@ PV_API int64_t pv_epoch_plan(const pv_psola_params *p, const pv_epoch_params *e,
  * [1 / max_rate, max_rate] keeps to it (DESIGN.md "Time-scale modification"); a call with a tile beyond it is refused.  The span, the prototype and the
  * window table share the 160 KiB of LDS of a compute unit: pv_tsm_create returns PV_ERR_UNSUPPORTED for a pair beyond that (max_period 4096 goes with
  * max_rate 1 only, 2048 and less with any).
- * Limits: for a monophonic voice; one plan serves all channels; unvoiced grains repeated at slow rates can buzz (their time direction is not alternated). */
+ * Limits: for a monophonic voice; one plan serves all channels; unvoiced grains repeated at slow rates can buzz (their time direction is not alternated
+ * here: pv_mirror_* below alternates it). */
 typedef struct pv_tsm_config {
     int32_t struct_size;     /* sizeof(pv_tsm_config) as the caller compiled it (PV_TSM_CONFIG_INIT sets it)                      */
     int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096                                             */
@@ -868,6 +869,59 @@ PV_API int pv_tsm_process_device(pv_tsm *h, const float *d_in, int64_t nin, int6
  * centre would reach 2^30 (grains before it may have been written). */
 PV_API int64_t pv_tsm_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
                            const double *rates, const int32_t *epochs, int32_t *grains, int64_t capacity, int64_t *output_len);
+
+/* ---- mirrored grains on the overlap-add path: a grain may read the input backwards, so that a repeated noise grain does not buzz (a separate handle) ---- */
+/* At a rate below 1 pv_tsm_plan uses every analysis mark of an unvoiced stretch two or three times; the same noise grain repeating at the mark spacing
+ * is heard as a tone at sample_rate / unvoiced_period.  TD-PSOLA's remedy is to alternate the time direction of the repeats.  A grain here is
+ * pv_tsm_process's {t, w, D, L} with one more bit: w = tf + 256 phi + 65536 m, m in {0, 1}, 0 <= w < 131072.  With m = 0 it is pv_tsm_process's far grain
+ * word for word (|D| < 2^30), and a table without mirrored grains gives pv_tsm_process's bits.  With m = 1 the grain is mirrored: output n reads the
+ * input at the real position D - n - phi / 256; D > -2^30, any larger int32 is allowed (D is a sum of two positions below 2^30).  The window and output
+ * rules do not change; the sample rule is the forward one with n - D replaced by D - n and nothing else (phi == 0 reads x[D - n] itself, else
+ * theta = 256 - phi, b = D - n - 1 and the 64 taps x[b - 31 + i] with weights P[|256 (i - 31) - theta|], i ascending).  The order of every sum stays a
+ * function of (g, i) alone: any partition of the output range into calls gives the same bits.
+ * What a call may read: pv_tsm_process's rule, with the source range of a mirrored grain that reaches the tile [j0, j1) running from
+ * D - min(j1, t + L) - 33 to D - max(j0, t - L) + 32; span(max_period, max_rate) and the 160 KiB rule of pv_tsm_create are unchanged, and a table of
+ * pv_mirror_plan whose rates lie within [1 / max_rate, max_rate] keeps to the span (DESIGN.md "Mirrored grains").
+ * Limits: pv_tsm's; with three or more uses of one mark the first and the third are both forward, so a component at twice the mark spacing stays. */
+typedef struct pv_mirror_config {
+    int32_t struct_size;     /* sizeof(pv_mirror_config) as the caller compiled it (PV_MIRROR_CONFIG_INIT sets it)                */
+    int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096                                             */
+    int32_t max_rate;        /* 1 .. 4: sizes the span, as pv_tsm_config                                                         */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_mirror_config;
+#define PV_MIRROR_CONFIG_INIT { (int32_t)sizeof(pv_mirror_config), 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_mirror pv_mirror;
+
+/* Config errors are returned before any device is touched, PV_ERR_UNSUPPORTED where pv_tsm_create returns it; failures are readable through
+ * pv_mirror_last_error(NULL). */
+PV_API int pv_mirror_create(const pv_mirror_config *cfg, pv_mirror **out);
+PV_API int pv_mirror_destroy(pv_mirror *h);
+PV_API const char *pv_mirror_last_error(const pv_mirror *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_mirror_set_stream(pv_mirror *h, void *hip_stream);
+PV_API int pv_mirror_synchronize(pv_mirror *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1, with pv_tsm_process's arguments and layout; grains is a HOST table, one for all
+ * channels.  Stateless.  Rejected with PV_ERR_ARGUMENT before any device work and with the output untouched: everything pv_tsm_process rejects, with
+ * the grain rules above (w of 131072 or more, a mirrored grain with D <= -2^30, a forward grain with |D| >= 2^30), and a tile that reads more than the
+ * span (the message names the grain, for a tile its first).  nch > max_channels: PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of
+ * whole tiles as pv_tsm_process: a piece stages the hull of its tiles' source ranges cut to the input. */
+PV_API int pv_mirror_process(pv_mirror *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains, float *out,
+                             int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains stay a host table), asynchronous on the handle's stream. */
+PV_API int pv_mirror_process_device(pv_mirror *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains,
+                                    float *d_out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* Pure host code: pv_tsm_plan with the direction of every grain.  mirror == 0: pv_tsm_plan's grains and output_len bit for bit.  mirror == 1 (any other
+ * value is refused): the walk, the marks, T, V, c, L and output_len do not change.  A grain held at (T, A) is a REUSE when a grain was held before it,
+ * that grain's analysis mark is this very A (the same double: the walk did not advance) and the record at A is unvoiced or there are no records.  A
+ * reuse takes the opposite direction of the grain before it; every other grain is forward, so a voiced grain is never mirrored.  A mirrored grain reads
+ * about its own mark (input A - (tau - T) lands at output tau): sq = floor(256 (T + A) + 1/2) in int64, D = (sq + 255) >> 8, phi = 256 D - sq,
+ * w = tf + 256 phi + 65536.  Returns and refuses as pv_tsm_plan (and refuses a plan whose mirrored D would pass int32). */
+PV_API int64_t pv_mirror_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
+                              const double *rates, const int32_t *epochs, int32_t mirror, int32_t *grains, int64_t capacity, int64_t *output_len);
 
 /* ---- harmony voices on the overlap-add path: several differently shifted copies of the voice summed into one output (a separate handle) ---- */
 /* A harmonizer: a third and a fifth above the lead, in key, on the same time base.  A call has nvoices voices, 1 <= nvoices <= 8.  Voice v is a far-grain

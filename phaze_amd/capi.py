@@ -49,6 +49,8 @@ EXPORTS = [
     "pv_harmony_process_device", "pv_harmony_ratios",
     "pv_takes_create", "pv_takes_destroy", "pv_takes_last_error", "pv_takes_set_stream", "pv_takes_synchronize", "pv_takes_process", "pv_takes_process_device",
     "pv_takes_tiles",
+    "pv_mirror_create", "pv_mirror_destroy", "pv_mirror_last_error", "pv_mirror_set_stream", "pv_mirror_synchronize", "pv_mirror_process",
+    "pv_mirror_process_device", "pv_mirror_plan",
 ]
 
 
@@ -119,6 +121,15 @@ class _HarmonyConfig(C.Structure):
 
 class _TakesConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+class _MirrorConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+def make_mirror_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_mirror_config with struct_size filled in (the C side's PV_MIRROR_CONFIG_INIT)."""
+    return _MirrorConfig(C.sizeof(_MirrorConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
 
 
 class _Take(C.Structure):
@@ -419,6 +430,17 @@ def load_library():
     L.pv_takes_tiles.argtypes = [C.POINTER(_TakesConfig), C.POINTER(_Take), C.c_int32, ip, C.c_int64]
     L.pv_takes_last_error.restype = C.c_char_p
     L.pv_takes_tiles.restype = C.c_int64
+    L.pv_mirror_create.argtypes = [C.POINTER(_MirrorConfig), C.POINTER(vp)]
+    L.pv_mirror_destroy.argtypes = [vp]
+    L.pv_mirror_last_error.argtypes = [vp]
+    L.pv_mirror_set_stream.argtypes = [vp, vp]
+    L.pv_mirror_synchronize.argtypes = [vp]
+    L.pv_mirror_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_mirror_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_mirror_plan.argtypes = [C.POINTER(_PsolaParams), C.POINTER(_EpochParams), ip, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), ip, C.c_int32, ip,
+                                 C.c_int64, C.POINTER(C.c_int64)]
+    L.pv_mirror_last_error.restype = C.c_char_p
+    L.pv_mirror_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1617,6 +1639,19 @@ def tsm_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period,
     """pv_tsm_plan: (far grains int32[ngrains, 4] = {t, tf + 256 phi, D, L} of Tsm.process, output_len).  epoch_plan with a read position beside the
     synthesis position: rates float64[nrec], the input samples consumed per output sample while the read position lies on record j (2: twice as fast,
     1/2: half speed; finite and positive, held within [1/4, 4]; None: 1, and then the grains are epoch_plan's in the far notation)."""
+    return _far_plan(None, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock)
+
+
+def mirror_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None, rates=None, epochs=None, min_strength=0, lock=0.125,
+                mirror=True):
+    """pv_mirror_plan: (grains int32[ngrains, 4] = {t, tf + 256 phi + 65536 m, D, L} of Mirror.process, output_len).  tsm_plan with the time direction of
+    every grain: with mirror=True every second use of an unvoiced analysis mark reads the input backwards about that mark (m = 1), which takes the buzz
+    out of noise repeated at rates below 1; voiced grains are never mirrored.  mirror=False: tsm_plan's grains bit for bit."""
+    return _far_plan(bool(mirror), records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock)
+
+
+def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock):
+    """The body of tsm_plan (mirror is None: pv_tsm_plan) and of mirror_plan (pv_mirror_plan with that mirror argument)."""
     L = load_library()
     r, nrec = _one_channel_records(records)
     rows = []
@@ -1640,12 +1675,16 @@ def tsm_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period,
     sp = spd.ctypes.data_as(dp) if spd is not None and nrec else None
     ep_ = ep.ctypes.data_as(ip) if ep is not None and nrec else None
     out_len = C.c_int64(0)
-    n = L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, None, 0, C.byref(out_len))
+    if mirror is None:
+        name, plan = "tsm_plan", lambda out, cap: L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, out, cap, C.byref(out_len))
+    else:
+        name, plan = "mirror_plan", lambda out, cap: L.pv_mirror_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, int(mirror), out, cap, C.byref(out_len))
+    n = plan(None, 0)
     if n < 0:
-        raise ValueError("tsm_plan: bad argument (epoch_plan's ranges, rates finite and positive, and the output must end below 2^30)")
+        raise ValueError(f"{name}: bad argument (epoch_plan's ranges, rates finite and positive, and the output must end below 2^30)")
     grains = np.zeros((n, 4), np.int32)
     if n:
-        L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, grains.ctypes.data_as(ip), n, C.byref(out_len))
+        plan(grains.ctypes.data_as(ip), n)
     return grains, int(out_len.value)
 
 
@@ -1695,37 +1734,89 @@ class Tsm(_Handle):
         rate: the input samples consumed per output sample, one number or one per f0 record (float64[nrec]: a tempo curve); 1/2 is half speed.
         The voice is corrected onto the scale in the same pass, as Psola.process_tuned does; strength = 0 leaves the pitch alone.  tracker and epochs as
         there.  x: float32[nch, n] (host).  Returns (y float32[nch, output_len], grains)."""
+        return _process_tuned(self, tsm_plan, x, sample_rate, rate, scale_mask, strength, retune, tracker, threshold, a4, epochs)
+
+
+def _process_tuned(self, plan, x, sample_rate, rate, scale_mask, strength, retune, tracker, threshold, a4, epochs):
+    """Tsm.process_tuned and Mirror.process_tuned: track, tune_ratios, `plan` (tsm_plan's arguments), process."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    one = x.ndim == 1
+    if one:
+        x = x[None, :]
+    own = tracker is None
+    if own:
+        max_lag = max(self.max_period, 3)
+        tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
+    try:
+        records = tracker.track(x[0], threshold)[0]
+    finally:
+        if own:
+            tracker.close()
+    nrec = records.shape[0]
+    ratios = tune_ratios(records, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+    rates = np.full(nrec, float(rate)) if np.ndim(rate) == 0 else np.ascontiguousarray(rate, dtype=np.float64)
+    if rates.shape != (nrec,):
+        raise ValueError(f"rate must be one number or one per f0 record ({nrec})")
+    min_period = tracker.min_lag
+    found = None
+    if epochs:
+        longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
+        marks = EpochTracker(2 * longest, tracker.hop, longest)
+        try:
+            found = marks.track(x[0], epoch_periods(records))[0]
+        finally:
+            marks.close()
+    grains, output_len = plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                              self.max_period, ratios=ratios, rates=rates, epochs=found)
+    y = self.process(x, grains, 0, output_len)
+    return (y[0] if one else y), grains
+
+
+class Mirror(_Handle):
+    """Overlap-add of grains that read the input in either time direction (pv_mirror_*): Tsm with one more bit per grain.  A grain int32[4] =
+    {t, tf + 256 phi + 65536 m, D, L}; with m = 0 it is Tsm's far grain (and a table without mirrored grains gives Tsm.process's bits), with m = 1 it
+    reads the input at D - n - phi / 256: backwards.  mirror_plan mirrors every second use of an unvoiced analysis mark, which takes the buzz out of
+    noise repeated at rates below 1.  The span, the LDS rule and the partition invariance are Tsm's."""
+
+    _prefix = "pv_mirror"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_mirror_config(max_period, max_rate, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_channels = max_period, max_rate, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    _grains = staticmethod(Psola._grains)
+
+    def process(self, x, grains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), grains: int32[ngrains, 4] -> float32[nch, nout], outputs out_first .. out_first + nout - 1 (default: n - out_first; pass
+        mirror_plan's output_len for a whole stretched signal)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         one = x.ndim == 1
         if one:
             x = x[None, :]
-        own = tracker is None
-        if own:
-            max_lag = max(self.max_period, 3)
-            tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
-        try:
-            records = tracker.track(x[0], threshold)[0]
-        finally:
-            if own:
-                tracker.close()
-        nrec = records.shape[0]
-        ratios = tune_ratios(records, sample_rate, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
-        rates = np.full(nrec, float(rate)) if np.ndim(rate) == 0 else np.ascontiguousarray(rate, dtype=np.float64)
-        if rates.shape != (nrec,):
-            raise ValueError(f"rate must be one number or one per f0 record ({nrec})")
-        min_period = tracker.min_lag
-        found = None
-        if epochs:
-            longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
-            marks = EpochTracker(2 * longest, tracker.hop, longest)
-            try:
-                found = marks.track(x[0], epoch_periods(records))[0]
-            finally:
-                marks.close()
-        grains, output_len = tsm_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
-                                      self.max_period, ratios=ratios, rates=rates, epochs=found)
-        y = self.process(x, grains, 0, output_len)
-        return (y[0] if one else y), grains
+        nch, n = x.shape
+        g, ng = self._grains(grains)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_mirror_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng, _fp(y), int(out_first), nout,
+                                              max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, grains, d_out, out_first, nout, out_stride):
+        """pv_mirror_process_device on raw device pointers (ints), asynchronous on the handle's stream; grains is a host table."""
+        g, ng = self._grains(grains)
+        self._check(self._L.pv_mirror_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng,
+                                                     C.c_void_p(d_out), out_first, nout, out_stride))
+
+    def process_tuned(self, x, sample_rate, rate=1.0, mirror=True, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0, epochs=False):
+        """Tsm.process_tuned with mirror_plan in place of tsm_plan: at rates below 1 the repeated unvoiced grains alternate their time direction.
+        mirror=False plans as Tsm.process_tuned does.  Returns (y float32[nch, output_len], grains)."""
+        def plan(*args, **kw):
+            return mirror_plan(*args, mirror=mirror, **kw)
+        return _process_tuned(self, plan, x, sample_rate, rate, scale_mask, strength, retune, tracker, threshold, a4, epochs)
 
 
 def harmony_ratios(records, sample_rate, degrees, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0):

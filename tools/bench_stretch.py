@@ -32,8 +32,12 @@ in all), each with its own table, periods 192 .. 208 moved by 1.25; (a) all at r
 on (1024, 4): tiles of mixed occupancy classes.  The yardstick is a loop of 256 pv_tsm_process_device calls on one Tsm of the same configuration, then one
 synchronise.  Input-resident; the host's validation, walk and upload are inside the timed call; the outputs are asserted equal before timing; three runs
 of each line, alternating, and their spread.
+With --mirror: only the mirrored-grain kernel (pv_mirror_process_device, max_period 1024, max_rate 2) on the --tsm workload at rate 1/2 with every second
+block of 64 records unvoiced: the plan with mirrored grains, the plan made with mirror = 0 through the same kernel, and that plan through
+pv_tsm_process_device (asserted equal bit for bit before timing); three runs of each line, alternating, and their spread.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony] [--takes]
+                                  [--mirror]
 """
 import argparse
 import json
@@ -266,6 +270,55 @@ def tsm_line(torch, phaze_amd, n, ratio, rate, steps, warmup):
             "hbm_fraction": (nin + nout) * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
 
 
+def mirror_lines(torch, phaze_amd, n, steps, warmup, runs=3):
+    """tsm_line's workload at rate 1/2 with every second block of 64 records unvoiced, so that half of the material is repeated noise grains.  Three lines
+    on the same input: pv_mirror_process_device on the plan with mirrored grains, the same kernel on the plan made with mirror = 0, and
+    pv_tsm_process_device on that plan (whose output the second line must equal bit for bit); `runs` runs of each, alternating."""
+    hop = 256
+    nin = n // 2
+    nrec = nin // hop
+    lag = 200 + (np.arange(nrec) // 64) % 17 - 8                       # psola_line's records
+    lag[(np.arange(nrec) // 64) % 2 == 1] = 0                          # no lag found: unvoiced
+    records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+    plan = (records, hop, hop // 2, nin, 256.0, 32, 1024, np.full(nrec, 1.25), np.full(nrec, 0.5))
+    mirrored, nout = phaze_amd.mirror_plan(*plan, mirror=True)
+    forward, nout_f = phaze_amd.mirror_plan(*plan, mirror=False)
+    assert nout == nout_f and mirrored.shape == forward.shape
+    x = (torch.rand((1, nin), device="cuda") - 0.5).contiguous()
+    ys = [torch.empty((1, nout), device="cuda") for _ in range(3)]
+    mh = phaze_amd.Mirror(1024, 2, max_channels=1, max_outputs=1024)
+    ts = phaze_amd.Tsm(1024, 2, max_channels=1, max_outputs=1024)
+    stream = torch.cuda.Stream()
+    mh.set_stream(stream.cuda_stream)
+    ts.set_stream(stream.cuda_stream)
+    calls = [("pv_mirror", "mirror = 1", mirrored, lambda: mh.process_device(x.data_ptr(), nin, nin, 1, mirrored, ys[0].data_ptr(), 0, nout, nout)),
+             ("pv_mirror", "mirror = 0", forward, lambda: mh.process_device(x.data_ptr(), nin, nin, 1, forward, ys[1].data_ptr(), 0, nout, nout)),
+             ("pv_tsm", "mirror = 0", forward, lambda: ts.process_device(x.data_ptr(), nin, nin, 1, forward, ys[2].data_ptr(), 0, nout, nout))]
+    torch.cuda.synchronize()
+    for _, _, _, fn in calls:
+        fn()
+    mh.synchronize()
+    ts.synchronize()
+    torch.cuda.synchronize()
+    assert torch.equal(ys[1], ys[2]), "pv_mirror and pv_tsm disagree on a plan without mirrored grains"
+    ms = [[] for _ in calls]
+    for _ in range(runs):
+        for k, (_, _, _, fn) in enumerate(calls):
+            ms[k].append(_time(torch, stream, fn, steps, warmup))
+    mh.close()
+    ts.close()
+    lines = []
+    for (kernel, label, grains, _), v in zip(calls, ms):
+        best = min(v)
+        lines.append({"kernel": kernel, "plan": label, "max_period": 1024, "max_rate": 2, "ratio": 1.25, "rate": 0.5, "channels": 1, "inputs": nin, "outputs": nout,
+                      "grains": int(grains.shape[0]), "mirrored_grains": int(np.sum((grains[:, 1] >> 16) & 1)), "ms_per_launch": round(best, 4),
+                      "ms_per_launch_runs": [round(t, 4) for t in v], "spread": round((max(v) - best) / best, 4), "outputs_per_s": nout / (best * 1e-3),
+                      "hbm_fraction": (nin + nout) * 4 / (best * 1e-3) / HBM_BYTES_PER_S})
+    lines[0]["against_pv_tsm"] = round(min(ms[0]) / min(ms[2]), 4)
+    lines[1]["against_pv_tsm"] = round(min(ms[1]) / min(ms[2]), 4)
+    return lines
+
+
 def harmony_lines(torch, phaze_amd, n, steps, warmup):
     hop = 256
     nrec = n // hop
@@ -416,9 +469,15 @@ def main():
     ap.add_argument("--tsm", action="store_true", help="only the overlap-add line and the time-scale modification lines at the rates 1, 1/2 and 2 (--psola-outputs outputs)")
     ap.add_argument("--harmony", action="store_true", help="only the harmony line (four voices, --psola-outputs outputs) and the four launches plus mix it replaces")
     ap.add_argument("--takes", action="store_true", help="only the per-take lines (256 takes, --psola-outputs outputs in all) and the loops of pv_tsm calls they replace")
+    ap.add_argument("--mirror", action="store_true", help="only the mirrored-grain lines: the --tsm workload at rate 1/2, half of its records unvoiced, through "
+                    "pv_mirror and pv_tsm")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.mirror:
+        for line in mirror_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
+            print(json.dumps(line), flush=True)
+        return
     if args.takes:
         for line in takes_lines(torch, phaze_amd, args.psola_outputs, 256, args.steps, args.warmup):
             print(json.dumps(line), flush=True)

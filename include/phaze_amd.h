@@ -55,7 +55,7 @@ typedef struct pv_handle pv_handle;
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
  *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
- *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*. */
+ *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*; its warped grains (formant shifting), pv_formant_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -922,6 +922,64 @@ PV_API int pv_mirror_process_device(pv_mirror *h, const float *d_in, int64_t nin
  * w = tf + 256 phi + 65536.  Returns and refuses as pv_tsm_plan (and refuses a plan whose mirrored D would pass int32). */
 PV_API int64_t pv_mirror_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
                               const double *rates, const int32_t *epochs, int32_t mirror, int32_t *grains, int64_t capacity, int64_t *output_len);
+
+/* ---- formant shifting on the overlap-add path: a grain may read the input at a step of its own, which moves the spectral envelope (a separate handle) ---- */
+/* The overlap-add path moves pitch and tempo and keeps the formants where they were; this moves them on purpose (the "throat" control).  A grain that reads
+ * its input at a step other than one sample per output sample is time-compressed or time-expanded, which scales its spectrum, and so the envelope, by that
+ * step; the grain spacing still sets the pitch.  A grain here is pv_tsm_process's {t, w, D, L} with a step: w = tf + 256 phi + 131072 z, 0 <= w < 2^27,
+ * bit 16 (pv_mirror's direction bit) 0.  z is the step s in 1/256: z = 0 means s = 256, else 128 <= z <= 512 and s = z; z = 256 is treated exactly as z = 0.
+ * With s = 256 the grain is pv_tsm_process's far grain word for word, and a table without warped grains gives pv_tsm_process's bits.  With s != 256 output
+ * n of the grain reads the input at the real position (t + tf / 256 - D - phi / 256) + (s / 256) (n - t - tf / 256), in exact integers: u = 256 (n - t) - tf,
+ * v = 256 (tf - phi) + s u, m = (t - D) + floor(v / 65536), r = v mod 65536; den = max(256, s), W = 32 for s <= 256 and 64 otherwise; tap i = 0 .. 2 W - 1
+ * reads x[m - W + 1 + i] with d = |(i - W + 1) 65536 - r|, q = d div den, rem = d mod den, weight 0 when q >= 8192, else
+ * fmaf(f32(rem) * (1.0f / f32(den)), P[q + 1] - P[q], P[q]) (pv_vari's weight rule: above s = 256 the cutoff falls by 256 / s, so a compressed grain does
+ * not alias); a = fmaf(w_i, x_i, a) and sum += w_i for i ascending, xt = a / sum; a tap whose weight is exactly 0 touches neither sum whatever its sample
+ * holds.  Window, output rule and summation order are pv_tsm_process's: any partition of the output range into calls gives the same bits.
+ * What a call may read: per tile of 1024 outputs the hull of its grains' source ranges (psola/pv_formant.h gives the range of a warped grain) may not exceed
+ * span(max_period, max_rate) = max_rate (1024 + 2 max_period) + 6 max_period + 192 samples; a table of pv_formant_plan whose rates lie within
+ * [1 / max_rate, max_rate] and whose warps lie within [1/2, 2] keeps to it.  The span, the prototype and the window table share the 160 KiB of LDS of a
+ * compute unit, so fewer pairs fit than pv_tsm's: max_period up to 3753 at max_rate 1, 2900 at 2, 2331 at 3, 1925 at 4; pv_formant_create returns
+ * PV_ERR_UNSUPPORTED beyond.
+ * Limits: pv_tsm's; no mirrored warped grains; pv_harmony_* and pv_takes_* keep unwarped grains; a warp above about twice the pitch ratio leaves grains
+ * longer than two of their periods (the planner's gap floor), which blurs the moved envelope. */
+typedef struct pv_formant_config {
+    int32_t struct_size;     /* sizeof(pv_formant_config) as the caller compiled it (PV_FORMANT_CONFIG_INIT sets it)              */
+    int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096 (with max_rate: the LDS rule above)          */
+    int32_t max_rate;        /* 1 .. 4: sizes the span, as pv_tsm_config                                                         */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_formant_config;
+#define PV_FORMANT_CONFIG_INIT { (int32_t)sizeof(pv_formant_config), 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_formant pv_formant;
+
+/* Config errors are returned before any device is touched, PV_ERR_UNSUPPORTED for a pair beyond the LDS rule; failures are readable through
+ * pv_formant_last_error(NULL). */
+PV_API int pv_formant_create(const pv_formant_config *cfg, pv_formant **out);
+PV_API int pv_formant_destroy(pv_formant *h);
+PV_API const char *pv_formant_last_error(const pv_formant *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_formant_set_stream(pv_formant *h, void *hip_stream);
+PV_API int pv_formant_synchronize(pv_formant *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1, with pv_tsm_process's arguments and layout; grains is a HOST table, one for all
+ * channels.  Stateless.  Rejected with PV_ERR_ARGUMENT before any device work and with the output untouched: everything pv_tsm_process rejects, with
+ * the grain rules above (w of 2^27 or more, a step of 1 .. 127 or above 512, a set bit 16), and a tile that reads more than the span (the message names the
+ * grain, for a tile its first).  nch > max_channels: PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of whole tiles as pv_tsm_process. */
+PV_API int pv_formant_process(pv_formant *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains, float *out,
+                              int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains stay a host table), asynchronous on the handle's stream. */
+PV_API int pv_formant_process_device(pv_formant *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, int64_t ngrains,
+                                     float *d_out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* Pure host code: pv_tsm_plan with one more row, warps[j], one step per f0 record, each within [1/2, 2] (else refused, as ratios are); above 1 the formants
+ * move up.  warps == NULL: pv_tsm_plan's grains and output_len bit for bit.  Else the grain held for the analysis mark A takes alpha = warps[record of A],
+ * voiced or not (consonants move with the vowels): s = floor(256 alpha + 1/2), z = 0 when s == 256 and s otherwise, and its half length starts from
+ * floor(period(A) / (s / 256.0) + 1/2) in place of floor(period(A) + 1/2); pv_tsm_plan's floors then apply unchanged (at least floor(gap / 2) + 2, at
+ * least 2, at most max_period).  Marks, read position, D, phi and output_len do not depend on warps.  Limit: where alpha is above about twice the ratio the
+ * gap floor lengthens the grain beyond two of its periods; alpha is not clamped.  Returns and refuses as pv_tsm_plan. */
+PV_API int64_t pv_formant_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
+                               const double *rates, const double *warps, const int32_t *epochs, int32_t *grains, int64_t capacity, int64_t *output_len);
 
 /* ---- harmony voices on the overlap-add path: several differently shifted copies of the voice summed into one output (a separate handle) ---- */
 /* A harmonizer: a third and a fifth above the lead, in key, on the same time base.  A call has nvoices voices, 1 <= nvoices <= 8.  Voice v is a far-grain

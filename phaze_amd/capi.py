@@ -51,6 +51,8 @@ EXPORTS = [
     "pv_takes_tiles",
     "pv_mirror_create", "pv_mirror_destroy", "pv_mirror_last_error", "pv_mirror_set_stream", "pv_mirror_synchronize", "pv_mirror_process",
     "pv_mirror_process_device", "pv_mirror_plan",
+    "pv_formant_create", "pv_formant_destroy", "pv_formant_last_error", "pv_formant_set_stream", "pv_formant_synchronize", "pv_formant_process",
+    "pv_formant_process_device", "pv_formant_plan",
 ]
 
 
@@ -130,6 +132,15 @@ class _MirrorConfig(C.Structure):
 def make_mirror_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
     """pv_mirror_config with struct_size filled in (the C side's PV_MIRROR_CONFIG_INIT)."""
     return _MirrorConfig(C.sizeof(_MirrorConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
+
+
+class _FormantConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+def make_formant_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_formant_config with struct_size filled in (the C side's PV_FORMANT_CONFIG_INIT)."""
+    return _FormantConfig(C.sizeof(_FormantConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
 
 
 class _Take(C.Structure):
@@ -441,6 +452,17 @@ def load_library():
                                  C.c_int64, C.POINTER(C.c_int64)]
     L.pv_mirror_last_error.restype = C.c_char_p
     L.pv_mirror_plan.restype = C.c_int64
+    L.pv_formant_create.argtypes = [C.POINTER(_FormantConfig), C.POINTER(vp)]
+    L.pv_formant_destroy.argtypes = [vp]
+    L.pv_formant_last_error.argtypes = [vp]
+    L.pv_formant_set_stream.argtypes = [vp, vp]
+    L.pv_formant_synchronize.argtypes = [vp]
+    L.pv_formant_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_formant_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_formant_plan.argtypes = [C.POINTER(_PsolaParams), C.POINTER(_EpochParams), ip, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  ip, ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.pv_formant_last_error.restype = C.c_char_p
+    L.pv_formant_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1650,18 +1672,28 @@ def mirror_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_peri
     return _far_plan(bool(mirror), records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock)
 
 
-def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock):
-    """The body of tsm_plan (mirror is None: pv_tsm_plan) and of mirror_plan (pv_mirror_plan with that mirror argument)."""
+def formant_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None, rates=None, warps=None, epochs=None, min_strength=0,
+                 lock=0.125):
+    """pv_formant_plan: (grains int32[ngrains, 4] = {t, tf + 256 phi + 131072 z, D, L} of Formant.process, output_len).  tsm_plan with one more row:
+    warps float64[nrec], the step of the grains of record j within [1/2, 2] (above 1 the formants move up); z is the step in 1/256, 0 where it is 256, and a
+    grain's half length starts from period / step.  warps=None: tsm_plan's grains bit for bit."""
+    return _far_plan(None, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock, warps, True)
+
+
+def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock, warps=None,
+              formant=False):
+    """The body of tsm_plan (mirror is None: pv_tsm_plan), of mirror_plan (pv_mirror_plan with that mirror argument) and of formant_plan (formant: pv_formant_plan
+    with the row warps)."""
     L = load_library()
     r, nrec = _one_channel_records(records)
     rows = []
-    for name, row in (("ratios", ratios), ("rates", rates)):
+    for name, row in (("ratios", ratios), ("rates", rates), ("warps", warps)):
         if row is not None:
             row = np.ascontiguousarray(row, dtype=np.float64)
             if row.shape != (nrec,):
                 raise ValueError(f"{name} must be float64[nrec]")
         rows.append(row)
-    rho, spd = rows
+    rho, spd, wrp = rows
     ep = None
     if epochs is not None:
         ep = np.ascontiguousarray(epochs, dtype=np.int32)
@@ -1675,7 +1707,10 @@ def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, mi
     sp = spd.ctypes.data_as(dp) if spd is not None and nrec else None
     ep_ = ep.ctypes.data_as(ip) if ep is not None and nrec else None
     out_len = C.c_int64(0)
-    if mirror is None:
+    if formant:
+        wp = wrp.ctypes.data_as(dp) if wrp is not None and nrec else None
+        name, plan = "formant_plan", lambda out, cap: L.pv_formant_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, wp, ep_, out, cap, C.byref(out_len))
+    elif mirror is None:
         name, plan = "tsm_plan", lambda out, cap: L.pv_tsm_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, out, cap, C.byref(out_len))
     else:
         name, plan = "mirror_plan", lambda out, cap: L.pv_mirror_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, ep_, int(mirror), out, cap, C.byref(out_len))
@@ -1816,6 +1851,58 @@ class Mirror(_Handle):
         mirror=False plans as Tsm.process_tuned does.  Returns (y float32[nch, output_len], grains)."""
         def plan(*args, **kw):
             return mirror_plan(*args, mirror=mirror, **kw)
+        return _process_tuned(self, plan, x, sample_rate, rate, scale_mask, strength, retune, tracker, threshold, a4, epochs)
+
+
+class Formant(_Handle):
+    """Formant shifting on the overlap-add path (pv_formant_*): Tsm with a step per grain.  A grain int32[4] = {t, tf + 256 phi + 131072 z, D, L}; z is the
+    step s in 1/256 (0: 256; else 128 .. 512).  With s = 256 it is Tsm's far grain (and a table without warped grains gives Tsm.process's bits); otherwise
+    the grain reads s / 256 input samples per output sample about its centre, which moves its spectral envelope by s / 256 while the grain spacing still
+    sets the pitch.  formant_plan writes the steps from one warp per f0 record.  The span is wider than Tsm's (max_rate (1024 + 2 max_period) +
+    6 max_period + 192), so fewer (max_period, max_rate) pairs fit the LDS; the partition invariance is Tsm's."""
+
+    _prefix = "pv_formant"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_formant_config(max_period, max_rate, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_channels = max_period, max_rate, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    _grains = staticmethod(Psola._grains)
+
+    def process(self, x, grains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), grains: int32[ngrains, 4] -> float32[nch, nout], outputs out_first .. out_first + nout - 1 (default: n - out_first; pass
+        formant_plan's output_len for a whole signal)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        g, ng = self._grains(grains)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_formant_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng, _fp(y), int(out_first), nout,
+                                               max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, grains, d_out, out_first, nout, out_stride):
+        """pv_formant_process_device on raw device pointers (ints), asynchronous on the handle's stream; grains is a host table."""
+        g, ng = self._grains(grains)
+        self._check(self._L.pv_formant_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if ng else None, ng,
+                                                      C.c_void_p(d_out), out_first, nout, out_stride))
+
+    def process_tuned(self, x, sample_rate, warp=1.0, rate=1.0, scale_mask=0xFFF, strength=1.0, retune=1.0, tracker=None, threshold=2458, a4=440.0, epochs=False):
+        """Tsm.process_tuned with formant_plan in place of tsm_plan.  warp: the factor the formants move by, within [1/2, 2], one number or one per f0 record
+        (float64[nrec]); warp=1.0 plans as Tsm.process_tuned does and gives its bits.  Returns (y float32[nch, output_len], grains)."""
+        def plan(records, *args, **kw):
+            nrec = np.asarray(records).reshape(-1, 4).shape[0]
+            warps = np.full(nrec, float(warp)) if np.ndim(warp) == 0 else np.ascontiguousarray(warp, dtype=np.float64)
+            if warps.shape != (nrec,):
+                raise ValueError(f"warp must be one number or one per f0 record ({nrec})")
+            return formant_plan(records, *args, warps=warps, **kw)
         return _process_tuned(self, plan, x, sample_rate, rate, scale_mask, strength, retune, tracker, threshold, a4, epochs)
 
 

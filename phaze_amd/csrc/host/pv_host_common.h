@@ -1,4 +1,4 @@
-// pv_host_common.h -- what the host sides of the thirteen handle types (psola/pv_mirror_capi.hip, pv_capi.hip, stretch/pv_stretch_capi.hip, stretch/pv_f0_capi.hip, resample/pv_resample_capi.hip,
+// pv_host_common.h -- what the host sides of the fourteen handle types (psola/pv_formant_capi.hip, psola/pv_mirror_capi.hip, pv_capi.hip, stretch/pv_stretch_capi.hip, stretch/pv_f0_capi.hip, resample/pv_resample_capi.hip,
 // resample/pv_pitch_capi.hip, resample/pv_vari_capi.hip, resample/pv_glide_capi.hip, psola/pv_psola_capi.hip, psola/pv_epoch_capi.hip, psola/pv_tsm_capi.hip, psola/pv_harmony_capi.hip, psola/pv_takes_capi.hip) share: error reporting, the liveness check, the HIP check macros, the device buffer that grows on demand and the
 // twiddle / window tables.  Host code only; everything here is generic over the handle struct H, which has `magic`, `err` and `stream` members.
 // It lives in host/ so that the identity of the kernel sources (every *.hip and *.h directly in csrc/, bench.py) does not move with a host-only edit.

@@ -35,9 +35,12 @@ of each line, alternating, and their spread.
 With --mirror: only the mirrored-grain kernel (pv_mirror_process_device, max_period 1024, max_rate 2) on the --tsm workload at rate 1/2 with every second
 block of 64 records unvoiced: the plan with mirrored grains, the plan made with mirror = 0 through the same kernel, and that plan through
 pv_tsm_process_device (asserted equal bit for bit before timing); three runs of each line, alternating, and their spread.
+With --formant: only the warped-grain kernel (pv_formant_process_device, max_period 1024, max_rate 2) on the --tsm workload at rate 1: the unwarped plan
+through pv_tsm_process_device and through the new kernel (asserted equal bit for bit before timing), and the same plan warped at 0.8 and at 1.5; three runs
+of each line, alternating, and their spread.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony] [--takes]
-                                  [--mirror]
+                                  [--mirror] [--formant]
 """
 import argparse
 import json
@@ -319,6 +322,58 @@ def mirror_lines(torch, phaze_amd, n, steps, warmup, runs=3):
     return lines
 
 
+def formant_lines(torch, phaze_amd, n, steps, warmup, runs=3):
+    """tsm_line's workload at rate 1 and ratio 1.25 (all voiced: every grain fractional).  Four lines on the same input: pv_tsm_process_device on the unwarped
+    plan, pv_formant_process_device on it (whose output must equal the first bit for bit), and pv_formant_process_device on the same plan warped at 0.8 and
+    at 1.5; `runs` runs of each, alternating."""
+    hop = 256
+    nin = n
+    nrec = nin // hop
+    lag = 200 + (np.arange(nrec) // 64) % 17 - 8                       # psola_line's records
+    records = np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+    plan = (records, hop, hop // 2, nin, 256.0, 32, 1024, np.full(nrec, 1.25), np.full(nrec, 1.0))
+    plain, nout = phaze_amd.formant_plan(*plan)
+    tables = {1.0: plain}
+    for warp in (0.8, 1.5):
+        tables[warp], nout_w = phaze_amd.formant_plan(*plan, warps=np.full(nrec, warp))
+        assert nout_w == nout and tables[warp].shape == plain.shape
+    x = (torch.rand((1, nin), device="cuda") - 0.5).contiguous()
+    ys = [torch.empty((1, nout), device="cuda") for _ in range(4)]
+    fh = phaze_amd.Formant(1024, 2, max_channels=1, max_outputs=1024)
+    ts = phaze_amd.Tsm(1024, 2, max_channels=1, max_outputs=1024)
+    stream = torch.cuda.Stream()
+    fh.set_stream(stream.cuda_stream)
+    ts.set_stream(stream.cuda_stream)
+    calls = [("pv_tsm", 1.0, lambda: ts.process_device(x.data_ptr(), nin, nin, 1, plain, ys[0].data_ptr(), 0, nout, nout)),
+             ("pv_formant", 1.0, lambda: fh.process_device(x.data_ptr(), nin, nin, 1, plain, ys[1].data_ptr(), 0, nout, nout)),
+             ("pv_formant", 0.8, lambda: fh.process_device(x.data_ptr(), nin, nin, 1, tables[0.8], ys[2].data_ptr(), 0, nout, nout)),
+             ("pv_formant", 1.5, lambda: fh.process_device(x.data_ptr(), nin, nin, 1, tables[1.5], ys[3].data_ptr(), 0, nout, nout))]
+    torch.cuda.synchronize()
+    for _, _, fn in calls:
+        fn()
+    fh.synchronize()
+    ts.synchronize()
+    torch.cuda.synchronize()
+    assert torch.equal(ys[0], ys[1]), "pv_formant and pv_tsm disagree on a plan without warped grains"
+    ms = [[] for _ in calls]
+    for _ in range(runs):
+        for k, (_, _, fn) in enumerate(calls):
+            ms[k].append(_time(torch, stream, fn, steps, warmup))
+    fh.close()
+    ts.close()
+    lines = []
+    for (kernel, warp, _), v in zip(calls, ms):
+        best, grains = min(v), tables[warp]
+        lines.append({"kernel": kernel, "warp": warp, "step": int(round(256 * warp)), "max_period": 1024, "max_rate": 2, "ratio": 1.25, "rate": 1.0, "channels": 1,
+                      "inputs": nin, "outputs": nout, "grains": int(grains.shape[0]), "warped_grains": int(np.sum((grains[:, 1] >> 17) != 0)),
+                      "mean_half_length": round(float(grains[:, 3].mean()), 1), "ms_per_launch": round(best, 4), "ms_per_launch_runs": [round(t, 4) for t in v],
+                      "spread": round((max(v) - best) / best, 4), "outputs_per_s": nout / (best * 1e-3), "hbm_fraction": (nin + nout) * 4 / (best * 1e-3) / HBM_BYTES_PER_S})
+    lines[1]["against_pv_tsm"] = round(min(ms[1]) / min(ms[0]), 4)
+    for k in (2, 3):
+        lines[k]["against_unwarped"] = round(min(ms[k]) / min(ms[1]), 4)
+    return lines
+
+
 def harmony_lines(torch, phaze_amd, n, steps, warmup):
     hop = 256
     nrec = n // hop
@@ -471,9 +526,15 @@ def main():
     ap.add_argument("--takes", action="store_true", help="only the per-take lines (256 takes, --psola-outputs outputs in all) and the loops of pv_tsm calls they replace")
     ap.add_argument("--mirror", action="store_true", help="only the mirrored-grain lines: the --tsm workload at rate 1/2, half of its records unvoiced, through "
                     "pv_mirror and pv_tsm")
+    ap.add_argument("--formant", action="store_true", help="only the warped-grain lines: the --tsm workload at rate 1 through pv_tsm and through pv_formant unwarped, "
+                    "warped at 0.8 and at 1.5")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.formant:
+        for line in formant_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
+            print(json.dumps(line), flush=True)
+        return
     if args.mirror:
         for line in mirror_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
             print(json.dumps(line), flush=True)

@@ -161,6 +161,19 @@ __device__ __forceinline__ pk::c32 mul_w16_inv_pk(pk::c32 o, int r)
     }
 }
 
+// One conjugate pair of the N = 1024 split pass (FWD) / c2r pass with that factor inside, as ONE asm statement (pk::pair_pass; r compile-time after unrolling)
+template <bool FWD, bool SGPR>
+__device__ __forceinline__ void pair_pass_w16(int r, pk::c32 a, pk::c32 b, pk::c32 w, pk::c32 s, pk::c32 &x, pk::c32 &y)
+{
+    const float c = 0.92387953251128675613f, sn = 0.38268343236508977173f, h = 0.70710678118654752440f;
+    switch (r) {
+    case 0: pk::pair_pass<0, FWD, SGPR>(a, b, w, s, s, x, y); break;       // (no factor: the operand is not named)
+    case 1: pk::pair_pass<1, FWD, SGPR>(a, b, w, pk::c32{c, sn}, s, x, y); break;
+    case 2: pk::pair_pass<2, FWD, SGPR>(a, b, w, pk::c32{h, h}, s, x, y); break;
+    default: pk::pair_pass<3, FWD, SGPR>(a, b, w, pk::c32{sn, c}, s, x, y); break;
+    }
+}
+
 // base-4 digit reversal over nd digits (fft.js's input order of a radix-4 DIT, bundle:468-508)
 __device__ __forceinline__ int digitrev4(int v, int nd)
 {
@@ -171,9 +184,15 @@ __device__ __forceinline__ int digitrev4(int v, int nd)
 
 // Register <-> lane transpose WITHOUT LDS: exchanges the register index (8 registers) with the HIGH three lane bits, one bit per stage (see
 // pv_wave_fft.h, "transpose 1 of the wave FFTs in registers"); used by the wave FFTs and by transpose 2 of the 8192-point workgroup FFT.
-template <int NDW>
+// SELECT (NDW = 2; the fp32-first pitchFactor >= 1 instances of pv_wave_kernel_1024): the last stage without its copies.  A bank-masked DPP move keeps the other lanes
+// of its destination, so the compiler copies A first: three instructions per dword pair.  Here A' = (lane bit 3 clear ? A : B[l ^ 8]) is a select with a DPP source into a
+// fresh register (v_cndmask_b32_dpp: vcc ? src1 : dpp(src0)), and B' the masked move into B from the A that is still there: two.  Written as asm, four dword pairs a
+// statement: the compiler does not know the statement's DPP reads, so the two wait states a DPP read needs behind the VALU write of its source (the permlane swaps of the
+// stage before) stand inside it -- the s_mov of the lane mask and one s_nop.
+template <int NDW, bool SELECT = false>
 __device__ __forceinline__ void transpose_hi3_regs(unsigned (&w)[8][NDW])
 {
+    static_assert(!SELECT || NDW == 2, "the select form is written for packed fp32 complex elements");
 #pragma unroll
     for (int k = 0; k < 4; k++)                       // reg bit 2 <-> lane bit 5
 #pragma unroll
@@ -190,6 +209,21 @@ __device__ __forceinline__ void transpose_hi3_regs(unsigned (&w)[8][NDW])
             w[k][d] = r[0]; w[k + 2][d] = r[1];
         }
     }
+    if constexpr (SELECT) {                           // reg bit 0 <-> lane bit 3
+        const unsigned long long keep = 0x00FF00FF00FF00FFull;      // lanes whose bit 3 is clear
+#pragma unroll
+        for (int k = 0; k < 8; k += 4) {
+            unsigned t[4];
+#define PV_SEL(T, A, B) "v_cndmask_b32_dpp " T ", " B ", " A ", vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"    \
+                        "v_mov_b32_dpp " B ", " A " row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            asm("s_mov_b64 vcc, %12\n\ts_nop 0\n\t" PV_SEL("%0", "%8", "%4") PV_SEL("%1", "%9", "%5") PV_SEL("%2", "%10", "%6") PV_SEL("%3", "%11", "%7")
+                : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "+v"(w[k + 1][0]), "+v"(w[k + 1][1]), "+v"(w[k + 3][0]), "+v"(w[k + 3][1])
+                : "v"(w[k][0]), "v"(w[k][1]), "v"(w[k + 2][0]), "v"(w[k + 2][1]), "s"(keep)
+                : "vcc");
+#undef PV_SEL
+            w[k][0] = t[0]; w[k][1] = t[1]; w[k + 2][0] = t[2]; w[k + 2][1] = t[3];
+        }
+    } else
 #pragma unroll
     for (int k = 0; k < 8; k += 2)                    // reg bit 0 <-> lane bit 3
 #pragma unroll

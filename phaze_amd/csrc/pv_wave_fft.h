@@ -149,7 +149,9 @@ __device__ __forceinline__ void lds_reads_issued() { __builtin_amdgcn_sched_barr
 #endif
 // One pass of the packed inverse FFT with its twiddle reads in front: tw[j * STRIDE + i] holds the twiddles of outputs 2 j and 2 j + 1.  Output 0 has none: of row 0
 // only the upper half is read (the dead half's registers would be reused at once, and their next writer would wait for the read to land).
-template <int STRIDE>
+// TRIM (pv_pk_math.h: TRIM_*): the fused / SGPR-operand forms of the packed helpers; the twiddle products stay one statement each, so the waits for the reads
+// issued here still stand between them, one by one.
+template <int STRIDE, int TRIM = 0>
 __device__ __forceinline__ void radix8_inv_twiddles_first(pk::c32 (&a)[8], const v4f *tw, int i)
 {
     const pk::c32 t1 = lds_read_here(reinterpret_cast<const pk::c32 *>(&tw[i]) + 1);
@@ -157,12 +159,12 @@ __device__ __forceinline__ void radix8_inv_twiddles_first(pk::c32 (&a)[8], const
 #pragma unroll
     for (int j = 1; j < 4; j++) t[j] = lds_read_here(&tw[j * STRIDE + i]);
     lds_reads_issued();
-    pk::radix8_inv(a);
-    a[1] = pk::cmul(a[1], t1);
+    pk::radix8_inv_t<TRIM>(a);
+    a[1] = pk::cmul_t<TRIM>(a[1], t1);
 #pragma unroll
     for (int j = 1; j < 4; j++) {
-        a[2 * j] = pk::cmul(a[2 * j], pk::c32{t[j].x, t[j].y});
-        a[2 * j + 1] = pk::cmul(a[2 * j + 1], pk::c32{t[j].z, t[j].w});
+        a[2 * j] = pk::cmul_t<TRIM>(a[2 * j], pk::c32{t[j].x, t[j].y});
+        a[2 * j + 1] = pk::cmul_t<TRIM>(a[2 * j + 1], pk::c32{t[j].z, t[j].w});
     }
 }
 // REGT1 = false keeps transpose 1 in LDS: needed when `l` is NOT the physical lane id (pv_wave2k_kernel relabels the lanes of odd frames at hop 128).
@@ -170,21 +172,21 @@ __device__ __forceinline__ void radix8_inv_twiddles_first(pk::c32 (&a)[8], const
 // and the split pass) -- same arithmetic, the forward phases' priorities.
 // st(3) stands in front of pass 3, behind the last transpose read: the caller of the inverse instance issues the reads of its window rows there, and the 26 packed
 // instructions of the pass hide them (the forward instance passes nothing and pays nothing).
-template <bool REGT1 = true, typename ST = NoStamp, bool FWDPH = false>
+template <bool REGT1 = true, typename ST = NoStamp, bool FWDPH = false, int TRIM = 0>
 __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, const v4f *TW1F4, const v4f *TW2F4, int l, ST st = ST{})
 {
     constexpr int PHX = FWDPH ? PH_FX : PH_IX, PHA = FWDPH ? PH_FA : PH_IA, PHP3 = FWDPH ? PH_FP3 : PH_IP3;
     constexpr bool MATH = !(PV_ABL & 4), XPOSE = !(PV_ABL & 8), TWE = (PV_TW_EARLY & (FWDPH ? 1 : 2)) != 0;
     const int lh = l >> 3, ll = l & 7;
     v4f *S4 = reinterpret_cast<v4f *>(S);
-    if (MATH && TWE) radix8_inv_twiddles_first<64>(a, TW1F4, l);
+    if (MATH && TWE) radix8_inv_twiddles_first<64, TRIM>(a, TW1F4, l);
     else if (MATH) {
-        pk::radix8_inv(a);
+        pk::radix8_inv_t<TRIM>(a);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const v4f t = TW1F4[j * 64 + l];
-            if (j) a[2 * j] = pk::cmul(a[2 * j], pk::c32{t.x, t.y});
-            a[2 * j + 1] = pk::cmul(a[2 * j + 1], pk::c32{t.z, t.w});
+            if (j) a[2 * j] = pk::cmul_t<TRIM>(a[2 * j], pk::c32{t.x, t.y});
+            a[2 * j + 1] = pk::cmul_t<TRIM>(a[2 * j + 1], pk::c32{t.z, t.w});
         }
     }
     st(0);
@@ -193,7 +195,7 @@ __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, 
         unsigned w[8][2];
 #pragma unroll
         for (int k = 0; k < 8; k++) { w[k][0] = __float_as_uint(a[k].x); w[k][1] = __float_as_uint(a[k].y); }
-        transpose_hi3_regs<2>(w);
+        transpose_hi3_regs<2, (TRIM & pk::TRIM_DPP) != 0>(w);
 #pragma unroll
         for (int k = 0; k < 8; k++) a[k] = pk::c32{__uint_as_float(w[k][0]), __uint_as_float(w[k][1])};
     } else if (XPOSE) {
@@ -207,14 +209,14 @@ __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, 
         pv_prio(PHA);
     }
     st(1);
-    if (MATH && TWE) radix8_inv_twiddles_first<8>(a, TW2F4, ll);
+    if (MATH && TWE) radix8_inv_twiddles_first<8, TRIM>(a, TW2F4, ll);
     else if (MATH) {
-        pk::radix8_inv(a);
+        pk::radix8_inv_t<TRIM>(a);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const v4f t = TW2F4[j * 8 + ll];
-            if (j) a[2 * j] = pk::cmul(a[2 * j], pk::c32{t.x, t.y});
-            a[2 * j + 1] = pk::cmul(a[2 * j + 1], pk::c32{t.z, t.w});
+            if (j) a[2 * j] = pk::cmul_t<TRIM>(a[2 * j], pk::c32{t.x, t.y});
+            a[2 * j + 1] = pk::cmul_t<TRIM>(a[2 * j + 1], pk::c32{t.z, t.w});
         }
     }
     st(2);
@@ -230,7 +232,7 @@ __device__ __forceinline__ void fft512_wave_inv_pk(pk::c32 (&a)[8], pk::c32 *S, 
         pv_prio(PHP3);
     }
     st(3);
-    if (MATH) pk::radix8_inv(a);
+    if (MATH) pk::radix8_inv_t<TRIM>(a);
 }
 
 }  // namespace

@@ -497,7 +497,8 @@ __device__ __forceinline__ void spectrum64_1024(const float2 (&raw)[8], const pk
 // first conjugation folded into the window product, the second into the split pass: with Zc = conj(Z), E' = Zc[k] + conj(Zc[512-k]), O' = Zc[k] - conj(Zc[512-k]),
 // T = conj(W^k) O':  X[k] = conj(E' + j T), X[512-k] = E' - j T.  wlfs = SC conj(W^l) is the c2r twiddle of the kernel (SC a power of two), isc = 1 / SC takes the
 // scale out again inside the FMAs: exact.
-template <bool REGT1, typename EMIT, typename EMIT256, typename ST = NoStamp>
+// TRIM (pv_pk_math.h: TRIM_*): the fused and SGPR-operand forms of the packed helpers and the copy-free register transpose, for the instances named at the kernel.
+template <bool REGT1, int TRIM = 0, typename EMIT, typename EMIT256, typename ST = NoStamp>
 __device__ __forceinline__ void spectrum32_1024(const float2 (&raw)[8], const pk::c32 (&hw)[8], unsigned char *smem, int l, pk::c32 wlfs, float isc_, EMIT emit, EMIT256 emit256, ST st = ST{})
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
@@ -507,7 +508,7 @@ __device__ __forceinline__ void spectrum32_1024(const float2 (&raw)[8], const pk
     pk::c32 zc[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) zc[r] = pk::mul_conj(pk::c32{raw[r].x, raw[r].y}, hw[r]);       // conj(z), z pre-halved like the fp64 form's
-    fft512_wave_inv_pk<REGT1, ST, true>(zc, reinterpret_cast<pk::c32 *>(smem), TW1F4, TW2F4, l, st);
+    fft512_wave_inv_pk<REGT1, ST, true, TRIM>(zc, reinterpret_cast<pk::c32 *>(smem), TW1F4, TW2F4, l, st);
     pv_prio(PH_SPLITX);
     // partner rows 4..7, read back reversed.  (l = 0, r = 0) reads one element past the rows: Z[512] = Z[0] is put there, and the pair k = 0 goes through the same
     // arithmetic as the others (E' = 2 Re, O' = 2 j Im, W^0 = 1: X[0] = 2 (Re Z0 + Im Z0), X[512] = 2 (Re Z0 - Im Z0), with the roundings of the closed form)
@@ -524,6 +525,12 @@ __device__ __forceinline__ void spectrum32_1024(const float2 (&raw)[8], const pk
     for (int r = 0; r < 4; r++) zm[r] = XCH[(3 - r) * 64 + 64 - l];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
+        if constexpr (TRIM & pk::TRIM_FUSE) {
+            pk::c32 xa, xb;                                                 // one statement per pair (pv_pk_math.h: pair_pass)
+            pair_pass_w16<true, (TRIM & pk::TRIM_SGPR) != 0>(r, zc[r], zm[r], wlfs, isc, xa, xb);
+            emit(r, xa, xb);
+            continue;
+        }
         const pk::c32 E = pk::add_conj(zc[r], zm[r]), O = pk::sub_conj(zc[r], zm[r]);
         const pk::c32 T = pk::cmul(mul_w16_inv_pk(O, r), wlfs);             // SC conj(W^{l + 64 r}) O'
         const pk::c32 xa = pk::conj_fma_j(T, isc, E), xb = pk::fnma_j(T, isc, E);
@@ -598,6 +605,9 @@ __global__ __launch_bounds__(64 * (RESIDENT ? RES_WAVES : WAVES), RESIDENT ? 1 :
 {
     static_assert(!F32 || (!FP64 && !AUX), "the fp32-first forward transform is a product path: neither the reference-width flavour nor the tap instance");
     constexpr int WGW = RESIDENT ? RES_WAVES : WAVES;                    // waves per workgroup of this instance
+    // The fp32-first batch instances of the pitchFactor >= 1 class -- the headline launch -- take the packed helpers in their fused forms, wave-uniform factors from
+    // SGPRs and the register transposes without copies (pv_pk_math.h: TRIM_*; profiles/frame_copies_after.md).  Every other instance compiles to what it was.
+    constexpr int TRIM = (SPREAD && F32 && !RESIDENT && !AUX) ? (pk::TRIM_FUSE | pk::TRIM_SGPR | pk::TRIM_DPP) : 0;
     constexpr int N = 1024, M = 512, H = 513;
     constexpr int HOP = 128 * S_ROWS, R = N / HOP, LROWS = 8 - S_ROWS;    // LROWS rows of carried accumulator
     const int l = threadIdx.x & 63;
@@ -828,7 +838,7 @@ resident_top:
 #else
             NoStamp st32;
 #endif
-            spectrum32_1024<PV_F32_REGT1>(raw, hw, smem, l, wlfs, 1.0f / SC,
+            spectrum32_1024<PV_F32_REGT1, TRIM>(raw, hw, smem, l, wlfs, 1.0f / SC,
                                           [&](int r, pk::c32 xa, pk::c32 xb) {
                                               MAG[4 + l + 64 * r] = mag32(xa);
                                               MAG[4 + 512 - l - 64 * r] = mag32(xb);
@@ -934,8 +944,9 @@ resident_top:
                 for (int j = 0; j < 4; j++) {
                     const int i = 2 * j;
                     const pk::c32 c2{__uint_as_float(mg[i + 2]), __uint_as_float(mg[i + 3])}, n2{__uint_as_float(nm[i]), __uint_as_float(nm[i + 1])};
-                    const pk::c32 d2 = pk::sub(c2, n2), s2 = pk::add(c2, n2);
-                    pk::c32 t2 = pk::fms(d2, d2, pk::mul(pk::fma(s2, RR, KK), s2));      // (c - n)^2 - (c + n) (K + R (c + n)): <= 0 inside the band
+                    pk::c32 t2;                                             // (c - n)^2 - (c + n) (K + R (c + n)): <= 0 inside the band
+                    if constexpr (TRIM & pk::TRIM_FUSE) t2 = pk::band_test<(TRIM & pk::TRIM_SGPR) != 0>(c2, n2, RR, KK);
+                    else { const pk::c32 d2 = pk::sub(c2, n2), s2 = pk::add(c2, n2); t2 = pk::fms(d2, d2, pk::mul(pk::fma(s2, RR, KK), s2)); }
                     if (j == 0 && l == 0) t2 = pk::c32{1.f, 1.f};            // bins 0, 1 and 511 are no candidates (pv:97-100)
                     if (j == 3 && l == 63) t2.y = 1.f;
                     tmin = fminf(fminf(tmin, t2.x), t2.y);
@@ -1388,6 +1399,7 @@ resident_top:
                 for (int r = 0; r < 4; r++) {
                     pk::c32 yk = *reinterpret_cast<const pk::c32 *>(Yb + ystr + YR * r), ym = *reinterpret_cast<const pk::c32 *>(Yb + ystr_m + YR * (3 - r));
                     if (r == 0 && l == 0) { yk.y = 0.f; ym.y = 0.f; }
+                    if constexpr (TRIM & pk::TRIM_FUSE) { pair_pass_w16<false, (TRIM & pk::TRIM_SGPR) != 0>(r, yk, ym, wlfs, scsc, zi[r], zb[r]); continue; }
                     const pk::c32 E = pk::add_conj(yk, ym), O = pk::sub_conj(yk, ym);
                     const pk::c32 c = pk::cmul(mul_w16_inv_pk(O, r), wlfs);
                     zi[r] = pk::fma_addj(E, scsc, c);
@@ -1419,7 +1431,7 @@ resident_top:
         stamps.mark(7);
         fft512_wave_inv_pk<true>(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, [&](int id) { hann_rows(id); if (id & 1) stamps.mark(8 + id); else stamps.mark(8 + id, true); });
 #else
-        if constexpr (HANN_EARLY) fft512_wave_inv_pk(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, hann_rows);
+        if constexpr (HANN_EARLY) fft512_wave_inv_pk<true, decltype(hann_rows), false, TRIM>(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l, hann_rows);
         else fft512_wave_inv_pk(zi, reinterpret_cast<pk::c32 *>(S32), TW1F4, TW2F4, l);
 #endif
         }

@@ -55,7 +55,8 @@ typedef struct pv_handle pv_handle;
  *     pv_onset_strength / _device, pv_transient_plan, pv_onsets_from_strength (pv_tempo_process is unchanged); the resampler and pitch handles, pv_resample_*, pv_pitch_*;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
  *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
- *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*; its warped grains (formant shifting), pv_formant_*. */
+ *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*; its warped grains (formant shifting), pv_formant_*;
+ *     pitch contour tracking, pv_contour_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -1103,6 +1104,73 @@ PV_API int pv_takes_process_device(pv_takes *h, const pv_take *takes, int32_t nt
  * tile's occupancy class, always 1 .. 4: where the rounded s would not fit the LDS at all, s is src_count itself and cls is 1.  Returns the number of tiles and writes at most `capacity` of them; -PV_ERR_* on failure, with the message in
  * pv_takes_last_error(NULL): nothing is written then, except that the records before a tile beyond the span may have been. */
 PV_API int64_t pv_takes_tiles(const pv_takes_config *cfg, const pv_take *takes, int32_t ntakes, int32_t *tiles, int64_t capacity);
+
+/* ---- pitch contour tracking: several candidate periods per frame (a separate handle) and the cheapest path through them ------------------- */
+/* pv_f0_track decides every frame alone, so a frame whose fundamental is weak reads an octave up.  Here a frame keeps K candidates and a path search
+ * chooses among them under a cost for jumping and for switching voicing.  The path's output is f0 records (four int32 {tau, c(tau - 1), c(tau),
+ * c(tau + 1)}, tau < 0 for an unvoiced frame, zeros for an empty one): pv_f0_period and every planner take it as they take pv_f0_track's.
+ * Candidates.  Frame geometry, the scale, d(tau), cum(tau) and c(tau) for tau = 0 .. max_lag are exactly pv_f0_track's, with the same limits.  A lag tau
+ * in [min_lag, max_lag - 1] is a dip when c(tau) < c(tau - 1) and c(tau) <= c(tau + 1); its key is ((c(tau) + (bias tau) div max_lag) << 16) | tau.  The
+ * frame's K candidates are the K dips of smallest key, in key order: slot k = {tau, c(tau - 1), c(tau), c(tau + 1)}, {0, 0, 0, 0} beyond the number of
+ * dips and in every slot of a silent frame or of one with a non-finite sample.  bias is per call, in [0, 16384], in units of 2^-14 over the whole lag
+ * range: c is normalised by a cumulative mean, so under noise the dips at multiples of the period come out slightly deeper than the one at the period,
+ * and the bias puts the shortest first (DESIGN.md "Pitch contour").  Every value is an exact integer function of the frame's samples. */
+typedef struct pv_contour_config {
+    int32_t struct_size;     /* sizeof(pv_contour_config) as the caller compiled it (PV_CONTOUR_CONFIG_INIT sets it)              */
+    int32_t window;          /* W, the samples summed per lag                                                                    */
+    int32_t hop;             /* samples between frames                                                                           */
+    int32_t min_lag;         /* the shortest period looked for                                                                   */
+    int32_t max_lag;         /* the lags computed; the longest period looked for is max_lag - 1                                  */
+    int32_t candidates;      /* K, the slots per frame, 1 .. 8 (0 => 8)                                                          */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_frames;      /* host-pointer calls: staging size in frames (0 => 256); longer calls go in pieces                 */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_contour_config;
+#define PV_CONTOUR_CONFIG_INIT { (int32_t)sizeof(pv_contour_config), 0, 0, 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_contour pv_contour;
+
+/* Config errors are returned before any device is touched; failures are readable through pv_contour_last_error(NULL). */
+PV_API int pv_contour_create(const pv_contour_config *cfg, pv_contour **out);
+PV_API int pv_contour_destroy(pv_contour *h);
+PV_API const char *pv_contour_last_error(const pv_contour *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_contour_set_stream(pv_contour *h, void *hip_stream);
+PV_API int pv_contour_synchronize(pv_contour *h);
+/* nframes frames of channels 0 .. nch-1: channel c reads in[c*in_stride .. + (nframes - 1) hop + W + max_lag) and writes the K slots of frame m to
+ * candidates[4 K (c*cand_stride + m) ..): cand_stride counts frames.  Rejected with PV_ERR_ARGUMENT before any device work and with the table untouched:
+ * a null buffer, a negative count, a bias outside [0, 16384] and, with nch > 1, strides below what a channel reads and writes.  nch > max_channels:
+ * PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of max_frames. */
+PV_API int pv_contour_track(pv_contour *h, const float *in, int32_t nch, int64_t nframes, int64_t in_stride, int32_t bias, int32_t *candidates,
+                            int64_t cand_stride);
+/* The same on DEVICE in / candidates pointers (candidates 16-byte aligned: a slot is one store), asynchronous on the handle's stream. */
+PV_API int pv_contour_track_device(pv_contour *h, const float *d_in, int32_t nch, int64_t nframes, int64_t in_stride, int32_t bias, int32_t *d_candidates,
+                                   int64_t cand_stride);
+
+/* Pure host code, integers only.  The cheapest path through the table of ONE channel: candidates holds nrec frames of K = p->candidates slots.  The
+ * states of frame m are its occupied slots (tau > 0) and the unvoiced state, index K.  Costs in int64:
+ *   o_m(s)      slot s: min(c0, 16384) + (bias tau) div max_lag.  Unvoiced: unvoiced_cost when slot 0 of the frame is occupied, else 0.
+ *   t(a -> b)   0 from unvoiced to unvoiced, voicing_cost between unvoiced and voiced either way, (2 jump_cost |tau_b - tau_a|) div (tau_a + tau_b)
+ *               between two slots: an octave either way costs two thirds of jump_cost.
+ *   D_0(s) = o_0(s), D_m(s) = o_m(s) + min_a (D_(m-1)(a) + t(a -> s)), the tie to the lowest a; the last state is the first argmin of D_(nrec-1).
+ * records[4 m ..) is the slot itself for a voiced state, slot 0 with tau negated for the unvoiced state, and zeros where slot 0 is empty; states, when
+ * not NULL, gets the state index per frame.  With the ranges below the largest intermediate is under 2^38 per frame and under 2^62 over 2^31 - 1
+ * frames.  PV_ERR_ARGUMENT with records untouched: a null pointer with nrec > 0, nrec negative or above 2^31 - 1, a parameter out of range, or a table
+ * with tau < 0, tau > 65535 or a negative c value.  nrec = 0 is PV_OK.  The back pointers (nrec (K + 1) bytes) are allocated inside: PV_ERR_DEVICE
+ * when the host is out of memory, as the create functions. */
+typedef struct pv_contour_params {
+    int32_t struct_size;     /* sizeof(pv_contour_params) as the caller compiled it (PV_CONTOUR_PARAMS_INIT sets it)              */
+    int32_t candidates;      /* K of the table, 1 .. 8                                                                           */
+    int32_t max_lag;         /* the tracker's, 3 .. 4096                                                                         */
+    int32_t bias;            /* 0 .. 16384, normally the bias the table was made with                                            */
+    int32_t unvoiced_cost;   /* 1 .. 16384: what pv_f0_track's threshold is to a single frame                                    */
+    int32_t voicing_cost;    /* 0 .. 2^20                                                                                        */
+    int32_t jump_cost;       /* 0 .. 2^20                                                                                        */
+    int32_t reserved;        /* must be 0                                                                                        */
+} pv_contour_params;
+#define PV_CONTOUR_PARAMS_INIT { (int32_t)sizeof(pv_contour_params), 8, 0, 1024, 2458, 2458, 16384, 0 }
+PV_API int pv_contour_path(const pv_contour_params *p, const int32_t *candidates, int64_t nrec, int32_t *records, int32_t *states);
 
 #ifdef __cplusplus
 }

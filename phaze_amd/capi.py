@@ -53,6 +53,8 @@ EXPORTS = [
     "pv_mirror_process_device", "pv_mirror_plan",
     "pv_formant_create", "pv_formant_destroy", "pv_formant_last_error", "pv_formant_set_stream", "pv_formant_synchronize", "pv_formant_process",
     "pv_formant_process_device", "pv_formant_plan",
+    "pv_contour_create", "pv_contour_destroy", "pv_contour_last_error", "pv_contour_set_stream", "pv_contour_synchronize", "pv_contour_track",
+    "pv_contour_track_device", "pv_contour_path",
 ]
 
 
@@ -89,6 +91,14 @@ class _GlideConfig(C.Structure):
 
 class _F0Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "window", "hop", "min_lag", "max_lag", "max_channels", "max_frames", "device_id", "flags")]
+
+
+class _ContourConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "window", "hop", "min_lag", "max_lag", "candidates", "max_channels", "max_frames", "device_id", "flags")]
+
+
+class _ContourParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "candidates", "max_lag", "bias", "unvoiced_cost", "voicing_cost", "jump_cost", "reserved")]
 
 
 class _TuneParams(C.Structure):
@@ -187,6 +197,16 @@ def make_psola_params(f0_hop, f0_center, input_len, unvoiced_period, min_period,
 def make_f0_config(window, hop, min_lag, max_lag, max_channels=1, max_frames=0, device_id=0, flags=0):
     """pv_f0_config with struct_size filled in (the C side's PV_F0_CONFIG_INIT)."""
     return _F0Config(C.sizeof(_F0Config), window, hop, min_lag, max_lag, max_channels, max_frames, device_id, flags)
+
+
+def make_contour_config(window, hop, min_lag, max_lag, candidates=8, max_channels=1, max_frames=0, device_id=0, flags=0):
+    """pv_contour_config with struct_size filled in (the C side's PV_CONTOUR_CONFIG_INIT)."""
+    return _ContourConfig(C.sizeof(_ContourConfig), window, hop, min_lag, max_lag, candidates, max_channels, max_frames, device_id, flags)
+
+
+def make_contour_params(candidates, max_lag, bias=1024, unvoiced_cost=2458, voicing_cost=2458, jump_cost=16384):
+    """pv_contour_params with struct_size filled in (the C side's PV_CONTOUR_PARAMS_INIT)."""
+    return _ContourParams(C.sizeof(_ContourParams), candidates, max_lag, bias, unvoiced_cost, voicing_cost, jump_cost, 0)
 
 
 def make_tune_params(f0_hop, f0_center, sample_rate, synthesis_hop, min_hop, max_hop, input_len, scale_mask=0xFFF, strength=1.0, retune=1.0, a4=440.0, shift=0):
@@ -463,6 +483,15 @@ def load_library():
                                   ip, ip, C.c_int64, C.POINTER(C.c_int64)]
     L.pv_formant_last_error.restype = C.c_char_p
     L.pv_formant_plan.restype = C.c_int64
+    L.pv_contour_create.argtypes = [C.POINTER(_ContourConfig), C.POINTER(vp)]
+    L.pv_contour_destroy.argtypes = [vp]
+    L.pv_contour_last_error.argtypes = [vp]
+    L.pv_contour_set_stream.argtypes = [vp, vp]
+    L.pv_contour_synchronize.argtypes = [vp]
+    L.pv_contour_track.argtypes = [vp, fp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64]
+    L.pv_contour_track_device.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64]
+    L.pv_contour_path.argtypes = [C.POINTER(_ContourParams), ip, C.c_int64, ip, ip]
+    L.pv_contour_last_error.restype = C.c_char_p
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1442,6 +1471,75 @@ class F0Tracker(_Handle):
     def track_device(self, d_in, nch, nframes, in_stride, d_records, rec_stride, threshold=2458):
         """pv_f0_track_device on raw device pointers (ints), asynchronous on the handle's stream; rec_stride counts records."""
         self._check(self._L.pv_f0_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, int(threshold), C.c_void_p(d_records), rec_stride))
+
+
+def contour_path(candidates, max_lag, bias=1024, unvoiced_cost=2458, voicing_cost=2458, jump_cost=16384, states=False):
+    """pv_contour_path: the f0 records int32[nrec, 4] of the cheapest path through the candidate table int32[nrec, K, 4] of ONE channel
+    (ContourTracker.candidates): per frame the states are its occupied slots and the unvoiced state K; unvoiced_cost is what a frame pays for being
+    called unvoiced while it has a candidate, voicing_cost what a change of voicing costs and jump_cost what a relative change of the period of 1 costs
+    (an octave: two thirds of it).  states=True returns (records, int32[nrec] state per frame)."""
+    L = load_library()
+    c = np.ascontiguousarray(candidates, dtype=np.int32)
+    if c.ndim != 3 or c.shape[2] != 4 or not 1 <= c.shape[1] <= 8:
+        raise ValueError("candidates must be int32[nrec, K, 4] with K in 1 .. 8: one channel")
+    nrec, K = c.shape[0], c.shape[1]
+    p = make_contour_params(K, int(max_lag), int(bias), int(unvoiced_cost), int(voicing_cost), int(jump_cost))
+    ip = C.POINTER(C.c_int32)
+    rec, st = np.zeros((nrec, 4), np.int32), np.zeros(nrec, np.int32)
+    rc = L.pv_contour_path(C.byref(p), c.ctypes.data_as(ip) if nrec else None, nrec, rec.ctypes.data_as(ip) if nrec else None,
+                           st.ctypes.data_as(ip) if states and nrec else None)
+    if rc == PV_ERR_DEVICE:
+        raise MemoryError("contour_path: out of host memory")
+    if rc != PV_OK:
+        raise ValueError("contour_path: bad argument (max_lag 3 .. 4096, bias 0 .. 16384, unvoiced_cost 1 .. 16384, voicing_cost and jump_cost 0 .. 2^20, "
+                         "0 <= tau <= 65535 and c values >= 0 in the table)")
+    return (rec, st) if states else rec
+
+
+class ContourTracker(_Handle):
+    """The pitch contour tracker (pv_contour_*): per frame the K best dips of YIN's c curve on block-scaled integers (candidates), and contour_path
+    through them (track).  track gives F0Tracker.track's records, so a ContourTracker goes wherever a tracker is taken:
+    Psola(...).process_tuned(x, rate, tracker=ContourTracker(...)).  Frame m of a channel reads x[m hop, m hop + window + max_lag).  Stateless: the
+    candidates of a stream analysed in pieces overlap by window + max_lag - hop samples; the path is per call."""
+
+    _prefix = "pv_contour"
+
+    def __init__(self, window, hop, min_lag, max_lag, candidates=8, max_channels=1, max_frames=0, device_id=0, bias=1024, voicing_cost=2458, jump_cost=16384):
+        self._create(make_contour_config(window, hop, min_lag, max_lag, candidates, max_channels, max_frames, device_id, 0))
+        self.window, self.hop, self.min_lag, self.max_lag, self.max_channels = window, hop, min_lag, max_lag, max_channels
+        self.K = candidates if candidates else 8
+        self.bias, self.voicing_cost, self.jump_cost = bias, voicing_cost, jump_cost
+
+    def reset(self):
+        """Nothing to reset: the tracker carries no state."""
+
+    def frames(self, n):
+        """How many frames fit n samples per channel."""
+        return max((n - self.window - self.max_lag) // self.hop + 1, 0)
+
+    def candidates(self, x, bias=None):
+        """x: float32[nch, n] (host) -> int32[nch, frames(n), K, 4]: slot k = {lag, c(lag - 1), c(lag), c(lag + 1)} of the dip with the k-th smallest key,
+        zeros beyond the number of dips."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        nch, n = x.shape
+        nframes = self.frames(n)
+        cand = np.zeros((nch, nframes, self.K, 4), np.int32)
+        self._check(self._L.pv_contour_track(self._h, _fp(x), nch, nframes, n, int(self.bias if bias is None else bias),
+                                             cand.ctypes.data_as(C.POINTER(C.c_int32)), nframes))
+        return cand
+
+    def track(self, x, threshold=2458):
+        """x: float32[nch, n] (host) -> int32[nch, frames(n), 4], F0Tracker.track's records: the candidates, then one path per channel with `threshold` as
+        the unvoiced cost."""
+        cand = self.candidates(x)
+        return np.stack([contour_path(c, self.max_lag, self.bias, threshold, self.voicing_cost, self.jump_cost) for c in cand]).reshape(cand.shape[0], -1, 4)
+
+    def track_device(self, d_in, nch, nframes, in_stride, d_candidates, cand_stride, bias=None):
+        """pv_contour_track_device on raw device pointers (ints), asynchronous on the handle's stream; cand_stride counts frames."""
+        self._check(self._L.pv_contour_track_device(self._h, C.c_void_p(d_in), nch, nframes, in_stride, int(self.bias if bias is None else bias),
+                                                    C.c_void_p(d_candidates), cand_stride))
 
 
 def psola_window():

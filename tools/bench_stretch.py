@@ -17,6 +17,8 @@ With --vari: the variable-ratio resampler (pv_vari_process_device) on the same s
 the same two hop rows, with its ratio to the stretch line.
 With --f0: only the f0 tracker (pv_f0_track_device) at W = 1024, max_lag = 1024, hop = 256, lags from 32, mono and 8 channels, --f0-frames frames per
 channel of a harmonic tone; frames/s counts channel-frames, and `macs_per_s` is frames/s times the W * max_lag multiply-adds of a frame's lag products.
+With --contour: the --f0 lines, then the same shapes and signals through the candidate kernel of the contour tracker (pv_contour_track_device) at K = 8, bias
+1024, in the same process, each with its ratio to the --f0 line of the same shape.
 With --psola: only the pitch-synchronous overlap-add kernel (pv_psola_process_device), 2^24 outputs mono, periods 192 .. 208 samples moved by 1.25; a
 launch includes the host's validation of the grain table, the walk that finds every tile's grains and the upload of both.
 With --epoch: only the epoch kernel (pv_epoch_track_device) at window 2048, hop 256, longest period 1024, mono and 8 channels, --f0-frames frames per
@@ -40,7 +42,7 @@ through pv_tsm_process_device and through the new kernel (asserted equal bit for
 of each line, alternating, and their spread.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony] [--takes]
-                                  [--mirror] [--formant]
+                                  [--mirror] [--formant] [--contour]
 """
 import argparse
 import json
@@ -197,6 +199,27 @@ def glide_line(torch, phaze_amd, kind, N, hs, T, steps, warmup):
     p.close()
     return {"kernel": "pv_glide", "schedule": kind, "fft": N, "synthesis_hop": hs, "channels": 1, "frames_per_channel": T, "ms_per_launch": round(ms, 4),
             "frames_per_s": T / (ms * 1e-3), "samples_per_s": total / (ms * 1e-3), "hbm_fraction": 2 * total * 4 / (ms * 1e-3) / HBM_BYTES_PER_S}
+
+
+def contour_line(torch, phaze_amd, W, hop, lo, ML, nch, T, steps, warmup, f0_ms):
+    """f0_line's signal through the candidate kernel at K = 8."""
+    K = 8
+    n = (T - 1) * hop + W + ML
+    k = torch.arange(n, device="cuda", dtype=torch.float32)
+    x = torch.stack([sum(torch.sin(2 * np.pi * h * k / (217.3 + 31 * c)) / h for h in range(1, 6)) for c in range(nch)]).contiguous() * 0.3
+    cand = torch.empty((nch, T, K, 4), dtype=torch.int32, device="cuda")
+    trk = phaze_amd.ContourTracker(W, hop, lo, ML, candidates=K, max_channels=nch, max_frames=1)
+    stream = torch.cuda.Stream()
+    trk.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    ms = _time(torch, stream, lambda: trk.track_device(x.data_ptr(), nch, T, n, cand.data_ptr(), T), steps, warmup)
+    trk.close()
+    filled = int((cand[:, :, :, 0] > 0).sum().item())
+    frames = nch * T
+    return {"kernel": "pv_contour", "window": W, "hop": hop, "min_lag": lo, "max_lag": ML, "candidates": K, "channels": nch, "frames_per_channel": T,
+            "slots_filled": filled, "ms_per_launch": round(ms, 4), "frames_per_s": frames / (ms * 1e-3), "macs_per_frame": W * ML,
+            "macs_per_s": frames * W * ML / (ms * 1e-3), "hbm_fraction": frames * (hop * 4 + 16 * K) / (ms * 1e-3) / HBM_BYTES_PER_S,
+            "ratio_to_f0": round(ms / f0_ms, 4)}
 
 
 def f0_line(torch, phaze_amd, W, hop, lo, ML, nch, T, steps, warmup):
@@ -518,6 +541,7 @@ def main():
     ap.add_argument("--vari", action="store_true", help="add the variable-ratio resampler lines and the pitch-curve lines")
     ap.add_argument("--f0", action="store_true", help="only the f0 tracker lines")
     ap.add_argument("--f0-frames", type=int, default=16384, help="frames per channel of the f0 lines")
+    ap.add_argument("--contour", action="store_true", help="the f0 tracker lines, then the same shapes through the contour tracker's candidate kernel at K = 8")
     ap.add_argument("--psola", action="store_true", help="only the pitch-synchronous overlap-add line")
     ap.add_argument("--psola-outputs", type=int, default=1 << 24, help="outputs of the overlap-add line")
     ap.add_argument("--epoch", action="store_true", help="only the epoch kernel lines (--f0-frames frames per channel)")
@@ -559,9 +583,15 @@ def main():
         for nch in (1, 8):
             print(json.dumps(epoch_line(torch, phaze_amd, 2048, 256, 1024, nch, args.f0_frames, args.steps, args.warmup)), flush=True)
         return
-    if args.f0:
+    if args.f0 or args.contour:
+        f0_ms = {}
         for nch in (1, 8):
-            print(json.dumps(f0_line(torch, phaze_amd, 1024, 256, 32, 1024, nch, args.f0_frames, args.steps, args.warmup)), flush=True)
+            line = f0_line(torch, phaze_amd, 1024, 256, 32, 1024, nch, args.f0_frames, args.steps, args.warmup)
+            f0_ms[nch] = line["ms_per_launch"]
+            print(json.dumps(line), flush=True)
+        if args.contour:
+            for nch in (1, 8):
+                print(json.dumps(contour_line(torch, phaze_amd, 1024, 256, 32, 1024, nch, args.f0_frames, args.steps, args.warmup, f0_ms[nch])), flush=True)
         return
     T = args.frames
     shapes = [(1024, 256, 320, 1, T), (2048, 512, 640, 2, T // 2), (4096, 1024, 1280, 8, T // 8)]

@@ -56,7 +56,7 @@ typedef struct pv_handle pv_handle;
  *     the variable-ratio resampler and the pitch-curve handle, pv_vari_*, pv_glide_*; the f0 tracker and the pitch-correction planner, pv_f0_*,
  *     pv_tune_plan; pitch-synchronous overlap-add, pv_psola_*; its epoch marks, pv_epoch_*; its time-scale modification, pv_tsm_*; its harmony voices,
  *     pv_harmony_*; its per-take plans, pv_takes_*; its mirrored grains, pv_mirror_*; its warped grains (formant shifting), pv_formant_*;
- *     pitch contour tracking, pv_contour_*. */
+ *     pitch contour tracking, pv_contour_*; full-grain harmony voices (mirrored and warped grains in every voice), pv_choir_*. */
 #define PV_ABI_VERSION 6
 
 /* Construction options.  Replaces `new PhaseVocoderProcessor(options)` (phase-vocoder.js:24-43,
@@ -1043,6 +1043,69 @@ PV_API int pv_harmony_process_device(pv_harmony *h, const float *d_in, int64_t n
  * nvoices outside [1, 8], a null degrees and |degrees[v]| > 24. */
 PV_API int64_t pv_harmony_ratios(const pv_tune_params *p, const int32_t *records, int64_t nrec, const int32_t *degrees, int32_t nvoices, double *ratios,
                                  int64_t capacity);
+
+/* ---- full-grain harmony voices on the overlap-add path: pv_harmony's voices, whose grains may be mirrored, warped or both (a separate handle) ---- */
+/* What a harmonizer is bought for: a third below with the formants lowered (a different singer, not a chipmunk) beside the lead at warp 1, all at half
+ * tempo without the unvoiced buzz, in one call.  pv_choir_* lifts the limits pv_formant_config states for its own handle: here a grain may be mirrored AND
+ * warped, and every voice of a call carries the full grain word.  The structure is pv_harmony_process's (nvoices voices, grains the concatenation of the
+ * voices' tables, voice_first, gains, one num / den per voice, the float32 gain fold in voice order, a skipped voice touches nothing); on tables of plain
+ * far grains the output is pv_harmony_process's bit for bit.
+ * A grain is {t, w, D, L} with w = tf + 256 phi + 65536 m + 131072 z, 0 <= w < 2^27: m is pv_mirror_process's direction bit and z pv_formant_process's step
+ * s in 1/256 (z = 0 means s = 256, else 128 <= z <= 512; z = 256 is treated exactly as z = 0).  t, L and the ordering are pv_tsm_process's; D > -2^30
+ * always and D < 2^30 only for a forward grain, as pv_mirror_process.  With m = 0, s = 256 the grain is pv_tsm_process's far grain word for word; with
+ * m = 1, s = 256 pv_mirror_process's mirrored grain; with m = 0, s != 256 pv_formant_process's warped grain.  With m = 1 and s != 256 output n of the grain
+ * reads the input at the real position (D - t - tf / 256 - phi / 256) - (s / 256) (n - t - tf / 256), in exact integers: u = 256 (n - t) - tf,
+ * v = -256 (tf + phi) - s u, mm = (D - t) + floor(v / 65536), r = v mod 65536; from (mm, r) on the sample rule is pv_formant_process's, unchanged (tap i
+ * reads x[mm - W + 1 + i] with d = |(i - W + 1) 65536 - r|).  At s = 256 that rule lands on the mirrored grain's positions and weights.
+ * What a call may read: per tile of 1024 outputs the HULL over the voices of their grains' source ranges (psola/pv_choir.h gives the range of every kind
+ * of grain) may not exceed span(max_period, max_rate) = max_rate (1024 + 2 max_period) + 6 max_period + 192 samples, pv_formant_config's span with its LDS
+ * rule: max_period up to 3753 at max_rate 1, 2900 at 2, 2331 at 3, 1925 at 4; pv_choir_create returns PV_ERR_UNSUPPORTED beyond.  A call with a tile beyond
+ * the span is refused, never clipped.  Voices planned by pv_choir_plan on one row of rates within [1 / max_rate, max_rate] with warps within [1/2, 2] keep
+ * to it (DESIGN.md "Choir").
+ * Limits: pv_harmony's (a monophonic voice; one row of rates for all voices; consonants add up nvoices-fold: the gains are the remedy) and the planner
+ * limit of pv_formant_plan (a warp above about twice the pitch ratio leaves grains longer than two of their periods); pv_takes_* keeps unwarped grains. */
+typedef struct pv_choir_config {
+    int32_t struct_size;     /* sizeof(pv_choir_config) as the caller compiled it (PV_CHOIR_CONFIG_INIT sets it)                  */
+    int32_t max_period;      /* the largest half length L a call may pass, 2 .. 4096 (with max_rate: the LDS rule above)          */
+    int32_t max_rate;        /* 1 .. 4: sizes the span, as pv_formant_config                                                     */
+    int32_t max_voices;      /* voices per call, 1 .. 8 (0 => 8)                                                                 */
+    int32_t max_channels;    /* channels per call (0 => 1), at most 65535                                                        */
+    int32_t max_outputs;     /* host-pointer calls: staging size in outputs (0 => 65536), rounded up to whole tiles of 1024       */
+    int32_t device_id;       /* HIP device ordinal                                                                               */
+    int32_t flags;           /* must be 0                                                                                        */
+} pv_choir_config;
+#define PV_CHOIR_CONFIG_INIT { (int32_t)sizeof(pv_choir_config), 0, 0, 0, 0, 0, 0, 0 }
+
+typedef struct pv_choir pv_choir;
+
+/* Config errors are returned before any device is touched, PV_ERR_UNSUPPORTED for a pair beyond the LDS rule; failures are readable through
+ * pv_choir_last_error(NULL). */
+PV_API int pv_choir_create(const pv_choir_config *cfg, pv_choir **out);
+PV_API int pv_choir_destroy(pv_choir *h);
+PV_API const char *pv_choir_last_error(const pv_choir *h);
+/* Use an externally owned hipStream_t; NULL => the handle's own stream. */
+PV_API int pv_choir_set_stream(pv_choir *h, void *hip_stream);
+PV_API int pv_choir_synchronize(pv_choir *h);
+/* Outputs [out_first, out_first + nout) of channels 0 .. nch-1, with pv_harmony_process's arguments and layout.  grains, voice_first and gains are HOST
+ * tables.  Stateless.  Rejected with PV_ERR_ARGUMENT before any device work and with the output untouched: everything pv_harmony_process rejects, with the
+ * grain rules above per voice (the message names voice and grain, the grain counted within its voice: a word of 2^27 or more or below 0, a step of
+ * 1 .. 127 or above 512, a forward grain with D >= 2^30, any grain with D <= -2^30, a half length outside [2, max_period], centres out of order), and a
+ * tile whose hull exceeds the span (the message names the tile and the first grain of its lowest voice).  nvoices > max_voices or nch > max_channels:
+ * PV_ERR_CAPACITY.  Host pointers, synchronous, staged in pieces of whole tiles as pv_harmony_process. */
+PV_API int pv_choir_process(pv_choir *h, const float *in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains, const int64_t *voice_first,
+                            int32_t nvoices, const float *gains, float *out, int64_t out_first, int64_t nout, int64_t out_stride);
+/* The same on DEVICE in / out pointers (grains, voice_first and gains stay host tables), asynchronous on the handle's stream. */
+PV_API int pv_choir_process_device(pv_choir *h, const float *d_in, int64_t nin, int64_t in_stride, int32_t nch, const int32_t *grains,
+                                   const int64_t *voice_first, int32_t nvoices, const float *gains, float *d_out, int64_t out_first, int64_t nout,
+                                   int64_t out_stride);
+/* Pure host code: pv_mirror_plan with pv_formant_plan's row warps.  warps == NULL: pv_mirror_plan's grains and output_len bit for bit; mirror == 0:
+ * pv_formant_plan's.  With both, L and z of every grain come from pv_formant_plan's rule (s = floor(256 warps[record of A] + 1/2), the half length starts
+ * from floor(period(A) / (s / 256.0) + 1/2)) and the direction, D and phi of a reuse from pv_mirror_plan's; a mirrored warped grain then reads about its own
+ * mark: the analysis mark A at its centre, and (s / 256) L either side of it.  Marks, read position and output_len depend on neither.  Returns and refuses
+ * as both planners do (mirror other than 0 or 1, a warp outside [1/2, 2]). */
+PV_API int64_t pv_choir_plan(const pv_psola_params *p, const pv_epoch_params *e, const int32_t *records, int64_t nrec, const double *ratios,
+                             const double *rates, const double *warps, const int32_t *epochs, int32_t mirror, int32_t *grains, int64_t capacity,
+                             int64_t *output_len);
 
 /* ---- per-take plans on the overlap-add path: one call plays K independently planned takes of different lengths (a separate handle) ---- */
 /* A take is one monophonic recording with its own plan: its own input, far-grain table, length and output range.  (It is not a voice of pv_harmony,

@@ -8,9 +8,9 @@ from .capi import (FLAG_FP64_FORWARD, FLAG_GENERIC_KERNEL, FLAG_HOST_CHANNEL_BOO
                    FLAG_WORKGROUP_KERNEL, PhaseVocoder, PvError, TimeStretch, build_library, library_path, load_library, pinned_empty, tempo_hops,
                    onsets_from_strength, transient_plan, Resampler, PitchStretch, resample_design, resample_count, VariResampler, PitchGlide, vari_prototype, vari_half_width, F0Tracker, f0_period, tune_plan,
                    Psola, tune_ratios, psola_plan, psola_window, EpochTracker, epoch_periods, epoch_plan, Tsm, tsm_plan, Harmony, harmony_ratios, Takes, takes_tiles, Mirror, mirror_plan, Formant, formant_plan,
-                   ContourTracker, contour_path, make_contour_config)
+                   ContourTracker, contour_path, make_contour_config, Choir, choir_plan, make_choir_config)
 
 __all__ = ["PhaseVocoder", "PvError", "TimeStretch", "build_library", "library_path", "load_library", "FLAG_GENERIC_KERNEL", "FLAG_STREAM_COPY", "FLAG_WORKGROUP_KERNEL",
            "FLAG_STREAM_PINNED_INPUT", "FLAG_STREAM_EVENT_WAIT", "FLAG_PERSISTENT_STREAM", "FLAG_TEST_NO_HDP_FLUSH", "FLAG_TEST_FAIL_SECOND_PIECE", "FLAG_HOST_CHANNEL_BOOKKEEPING", "FLAG_FP64_FORWARD", "pinned_empty", "tempo_hops", "onsets_from_strength", "transient_plan", "Resampler", "PitchStretch", "resample_design", "resample_count", "VariResampler", "PitchGlide", "vari_prototype", "vari_half_width", "F0Tracker", "f0_period", "tune_plan",
            "Psola", "tune_ratios", "psola_plan", "psola_window", "EpochTracker", "epoch_periods", "epoch_plan", "Tsm", "tsm_plan", "Harmony", "harmony_ratios", "Takes", "takes_tiles", "Mirror", "mirror_plan", "Formant", "formant_plan",
-           "ContourTracker", "contour_path", "make_contour_config"]
+           "ContourTracker", "contour_path", "make_contour_config", "Choir", "choir_plan", "make_choir_config"]

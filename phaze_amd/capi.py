@@ -55,6 +55,8 @@ EXPORTS = [
     "pv_formant_process_device", "pv_formant_plan",
     "pv_contour_create", "pv_contour_destroy", "pv_contour_last_error", "pv_contour_set_stream", "pv_contour_synchronize", "pv_contour_track",
     "pv_contour_track_device", "pv_contour_path",
+    "pv_choir_create", "pv_choir_destroy", "pv_choir_last_error", "pv_choir_set_stream", "pv_choir_synchronize", "pv_choir_process", "pv_choir_process_device",
+    "pv_choir_plan",
 ]
 
 
@@ -151,6 +153,15 @@ class _FormantConfig(C.Structure):
 def make_formant_config(max_period, max_rate=1, max_channels=1, max_outputs=0, device_id=0, flags=0):
     """pv_formant_config with struct_size filled in (the C side's PV_FORMANT_CONFIG_INIT)."""
     return _FormantConfig(C.sizeof(_FormantConfig), max_period, max_rate, max_channels, max_outputs, device_id, flags)
+
+
+class _ChoirConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_period", "max_rate", "max_voices", "max_channels", "max_outputs", "device_id", "flags")]
+
+
+def make_choir_config(max_period, max_rate=1, max_voices=0, max_channels=1, max_outputs=0, device_id=0, flags=0):
+    """pv_choir_config with struct_size filled in (the C side's PV_CHOIR_CONFIG_INIT)."""
+    return _ChoirConfig(C.sizeof(_ChoirConfig), max_period, max_rate, max_voices, max_channels, max_outputs, device_id, flags)
 
 
 class _Take(C.Structure):
@@ -492,6 +503,17 @@ def load_library():
     L.pv_contour_track_device.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64]
     L.pv_contour_path.argtypes = [C.POINTER(_ContourParams), ip, C.c_int64, ip, ip]
     L.pv_contour_last_error.restype = C.c_char_p
+    L.pv_choir_create.argtypes = [C.POINTER(_ChoirConfig), C.POINTER(vp)]
+    L.pv_choir_destroy.argtypes = [vp]
+    L.pv_choir_last_error.argtypes = [vp]
+    L.pv_choir_set_stream.argtypes = [vp, vp]
+    L.pv_choir_synchronize.argtypes = [vp]
+    L.pv_choir_process.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int32, ip, C.POINTER(C.c_int64), C.c_int32, fp, fp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_choir_process_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, ip, C.POINTER(C.c_int64), C.c_int32, fp, vp, C.c_int64, C.c_int64, C.c_int64]
+    L.pv_choir_plan.argtypes = [C.POINTER(_PsolaParams), C.POINTER(_EpochParams), ip, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                ip, C.c_int32, ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.pv_choir_last_error.restype = C.c_char_p
+    L.pv_choir_plan.restype = C.c_int64
     L.pv_process_begin.argtypes = [vp, C.POINTER(fp), C.c_int32, C.c_int32, C.c_float]
     L.pv_process_end.argtypes = [vp, C.POINTER(fp)]
     L.pv_device_count.argtypes = [C.POINTER(C.c_int32)]
@@ -1778,10 +1800,20 @@ def formant_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_per
     return _far_plan(None, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock, warps, True)
 
 
+def choir_plan(records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios=None, rates=None, warps=None, epochs=None, min_strength=0,
+               lock=0.125, mirror=True):
+    """pv_choir_plan: (grains int32[ngrains, 4] = {t, tf + 256 phi + 65536 m + 131072 z, D, L} of one voice of Choir.process, output_len).  mirror_plan with
+    formant_plan's row warps: warps=None gives mirror_plan's grains bit for bit, mirror=False formant_plan's.  With both, every grain takes its step and its
+    half length from formant_plan's rule and a reuse of an unvoiced mark its direction, D and phi from mirror_plan's, so a mirrored warped grain reads
+    about its own mark."""
+    return _far_plan(bool(mirror), records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock, warps,
+                     choir=True)
+
+
 def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, min_period, max_period, ratios, rates, epochs, min_strength, lock, warps=None,
-              formant=False):
-    """The body of tsm_plan (mirror is None: pv_tsm_plan), of mirror_plan (pv_mirror_plan with that mirror argument) and of formant_plan (formant: pv_formant_plan
-    with the row warps)."""
+              formant=False, choir=False):
+    """The body of tsm_plan (mirror is None: pv_tsm_plan), of mirror_plan (pv_mirror_plan with that mirror argument), of formant_plan (formant: pv_formant_plan
+    with the row warps) and of choir_plan (choir: pv_choir_plan with both)."""
     L = load_library()
     r, nrec = _one_channel_records(records)
     rows = []
@@ -1805,7 +1837,10 @@ def _far_plan(mirror, records, f0_hop, f0_center, input_len, unvoiced_period, mi
     sp = spd.ctypes.data_as(dp) if spd is not None and nrec else None
     ep_ = ep.ctypes.data_as(ip) if ep is not None and nrec else None
     out_len = C.c_int64(0)
-    if formant:
+    if choir:
+        wp = wrp.ctypes.data_as(dp) if wrp is not None and nrec else None
+        name, plan = "choir_plan", lambda out, cap: L.pv_choir_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, wp, ep_, int(mirror), out, cap, C.byref(out_len))
+    elif formant:
         wp = wrp.ctypes.data_as(dp) if wrp is not None and nrec else None
         name, plan = "formant_plan", lambda out, cap: L.pv_formant_plan(C.byref(p), C.byref(e), rp, nrec, qp, sp, wp, ep_, out, cap, C.byref(out_len))
     elif mirror is None:
@@ -2116,6 +2151,100 @@ class Harmony(_Handle):
                 marks.close()
         plans = [tsm_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
                           self.max_period, ratios=ratios[v], rates=rates, epochs=found) for v in range(nv)]
+        tables = [g for g, _ in plans]
+        y = self.process(x, tables, np.full(nv, 1.0 / nv, np.float32) if gains is None else gains, 0, plans[0][1])
+        return (y[0] if one else y), tables
+
+
+class Choir(_Handle):
+    """Full-grain harmony voices on the overlap-add path (pv_choir_*): Harmony whose voices carry the full grain word.  A grain int32[4] =
+    {t, tf + 256 phi + 65536 m + 131072 z, D, L}: m is Mirror's direction bit and z Formant's step, and a grain may have both, in which case it reads
+    s / 256 input samples per output sample DOWNWARDS from D - t - tf / 256 - phi / 256 at its centre.  On plain far-grain tables the output is
+    Harmony.process's bit for bit; one voice at gain 1 gives Mirror.process's or Formant.process's values.  The mix, the hull staged once per tile and the
+    partition invariance are Harmony's; the span and the (max_period, max_rate) pairs that fit the LDS are Formant's.  choir_plan writes one voice's
+    table."""
+
+    _prefix = "pv_choir"
+    _fft_size_is_value_error = False
+
+    def __init__(self, max_period, max_rate=2, max_voices=8, max_channels=1, max_outputs=0, device_id=0):
+        self._create(make_choir_config(max_period, max_rate, max_voices, max_channels, max_outputs, device_id, 0))
+        self.max_period, self.max_rate, self.max_voices, self.max_channels = max_period, max_rate, max_voices, max_channels
+
+    def reset(self):
+        """Nothing to reset: the handle carries no signal state."""
+
+    _tables = staticmethod(Harmony._tables)
+
+    def process(self, x, tables, gains, out_first=0, nout=None):
+        """x: float32[nch, n] (host), tables: a list of grain arrays int32[., 4], one per voice, gains: [V] or [V, nch] -> float32[nch, nout], outputs
+        out_first .. out_first + nout - 1 (default: n - out_first; pass choir_plan's output_len for a whole stretched signal)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nch, n = x.shape
+        g, first, w = self._tables(tables, gains, nch)
+        nout = n - out_first if nout is None else int(nout)
+        y = np.zeros((nch, max(nout, 0)), np.float32)
+        self._check(self._L.pv_choir_process(self._h, _fp(x), n, n, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if g.size else None,
+                                             first.ctypes.data_as(C.POINTER(C.c_int64)), len(first) - 1, _fp(w), _fp(y), int(out_first), nout, max(nout, 0)))
+        return y[0] if one else y
+
+    def process_device(self, d_in, nin, in_stride, nch, tables, gains, d_out, out_first, nout, out_stride):
+        """pv_choir_process_device on raw device pointers (ints), asynchronous on the handle's stream; tables and gains are host tables."""
+        g, first, w = self._tables(tables, gains, nch)
+        self._check(self._L.pv_choir_process_device(self._h, C.c_void_p(d_in), nin, in_stride, nch, g.ctypes.data_as(C.POINTER(C.c_int32)) if g.size else None,
+                                                    first.ctypes.data_as(C.POINTER(C.c_int64)), len(first) - 1, _fp(w), C.c_void_p(d_out), out_first, nout,
+                                                    out_stride))
+
+    def process_tuned(self, x, sample_rate, degrees=(0, 2, 4), warps=None, gains=None, rate=1.0, mirror=False, scale_mask=0xFFF, strength=1.0, retune=1.0,
+                      tracker=None, threshold=2458, a4=440.0, epochs=False):
+        """Harmony.process_tuned with choir_plan in place of tsm_plan: one f0 track, optionally one epoch track, harmony_ratios, one choir_plan per voice on
+        the same row of rates, and one kernel call.  warps: None (no voice is warped), or one entry per voice, each one number or one per f0 record
+        (float64[nrec]) within [1/2, 2]: the factor the formants of that voice move by.  mirror: at rates below 1 the repeated unvoiced grains of every
+        voice alternate their time direction.  warps=None, mirror=False plans as Harmony.process_tuned does and gives its bits.  Returns
+        (y float32[nch, output_len], tables): output_len is voice 0's."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        nv = len(degrees)
+        if warps is not None and len(warps) != nv:
+            raise ValueError(f"warps must be None or have one entry per voice ({nv})")
+        own = tracker is None
+        if own:
+            max_lag = max(self.max_period, 3)
+            tracker = F0Tracker(1024, 256, max(2, min(32, max_lag // 2)), max_lag)
+        try:
+            records = tracker.track(x[0], threshold)[0]
+        finally:
+            if own:
+                tracker.close()
+        nrec = records.shape[0]
+        ratios = harmony_ratios(records, sample_rate, degrees, scale_mask=scale_mask, strength=strength, retune=retune, a4=a4)
+        rates = np.full(nrec, float(rate)) if np.ndim(rate) == 0 else np.ascontiguousarray(rate, dtype=np.float64)
+        if rates.shape != (nrec,):
+            raise ValueError(f"rate must be one number or one per f0 record ({nrec})")
+        rows = []
+        for v in range(nv):
+            row = None
+            if warps is not None:
+                row = np.full(nrec, float(warps[v])) if np.ndim(warps[v]) == 0 else np.ascontiguousarray(warps[v], dtype=np.float64)
+                if row.shape != (nrec,):
+                    raise ValueError(f"warps[{v}] must be one number or one per f0 record ({nrec})")
+            rows.append(row)
+        min_period = tracker.min_lag
+        found = None
+        if epochs:
+            longest = min(tracker.max_lag, 2048, (tracker.window + tracker.max_lag) // 2)
+            marks = EpochTracker(2 * longest, tracker.hop, longest)
+            try:
+                found = marks.track(x[0], epoch_periods(records))[0]
+            finally:
+                marks.close()
+        plans = [choir_plan(records, tracker.hop, (tracker.window + tracker.max_lag) // 2, x.shape[1], float(min(max(256, min_period), self.max_period)), min_period,
+                            self.max_period, ratios=ratios[v], rates=rates, warps=rows[v], epochs=found, mirror=mirror) for v in range(nv)]
         tables = [g for g, _ in plans]
         y = self.process(x, tables, np.full(nv, 1.0 / nv, np.float32) if gains is None else gains, 0, plans[0][1])
         return (y[0] if one else y), tables

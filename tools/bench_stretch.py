@@ -40,9 +40,13 @@ pv_tsm_process_device (asserted equal bit for bit before timing); three runs of 
 With --formant: only the warped-grain kernel (pv_formant_process_device, max_period 1024, max_rate 2) on the --tsm workload at rate 1: the unwarped plan
 through pv_tsm_process_device and through the new kernel (asserted equal bit for bit before timing), and the same plan warped at 0.8 and at 1.5; three runs
 of each line, alternating, and their spread.
+With --choir: only the full-grain harmony kernel (pv_choir_process_device, max_period 1024, max_rate 2) on the --harmony workload: pv_harmony_process_device
+on the four plain tables, pv_choir_process_device on the same tables (asserted equal bit for bit before timing), and pv_choir_process_device on four voices
+planned by choir_plan at rate 1/2 with mirror on and the warps 1, 0.8, 1.25 and 0.8, every second block of 64 records unvoiced so that the mirrored warped
+grains exist; three runs of each line, alternating, and their spread.
 
     python tools/bench_stretch.py [--steps 10] [--warmup 3] [--frames 1048576] [--vari] [--f0 [--f0-frames 16384]] [--psola] [--epoch] [--tsm] [--harmony] [--takes]
-                                  [--mirror] [--formant] [--contour]
+                                  [--mirror] [--formant] [--contour] [--choir]
 """
 import argparse
 import json
@@ -441,6 +445,72 @@ def harmony_lines(torch, phaze_amd, n, steps, warmup):
     return fused, apart
 
 
+def choir_lines(torch, phaze_amd, n, steps, warmup, runs=3):
+    """harmony_lines' workload (four voices at the degrees (0, 2, 4, -3) of C major, gains 1/4, 2^24 outputs mono).  Three lines: pv_harmony_process_device on
+    the plain tables, pv_choir_process_device on the same tables (whose output must equal the first bit for bit), and pv_choir_process_device on the voices
+    planned at rate 1/2 with mirror on and the warps 1, 0.8, 1.25, 0.8, every second block of 64 records unvoiced (mirror_lines' records) so that half of the
+    material is repeated noise grains in alternating directions; `runs` runs of each, alternating."""
+    hop = 256
+    degrees, warps = (0, 2, 4, -3), (1.0, 0.8, 1.25, 0.8)
+    nv = len(degrees)
+    gains = np.full(nv, 1.0 / nv, np.float32)
+
+    def records_of(nrec, noise):
+        lag = 200 + (np.arange(nrec) // 64) % 17 - 8                   # psola_line's records
+        if noise:
+            lag[(np.arange(nrec) // 64) % 2 == 1] = 0                  # no lag found: unvoiced
+        return np.stack([lag, np.full(nrec, 700), np.zeros(nrec, np.int64), np.full(nrec, 324)], axis=1).astype(np.int32)
+
+    nrec = n // hop
+    records = records_of(nrec, False)
+    ratios = phaze_amd.harmony_ratios(records, 48000.0, degrees, scale_mask=0xAB5)
+    plans = [phaze_amd.tsm_plan(records, hop, hop // 2, n, 256.0, 32, 1024, ratios[v], np.ones(nrec)) for v in range(nv)]
+    plain, nout = [g for g, _ in plans], plans[0][1]
+    nin2 = n // 2
+    nrec2 = nin2 // hop
+    records2 = records_of(nrec2, True)
+    ratios2 = phaze_amd.harmony_ratios(records2, 48000.0, degrees, scale_mask=0xAB5)
+    plans2 = [phaze_amd.choir_plan(records2, hop, hop // 2, nin2, 256.0, 32, 1024, ratios2[v], np.full(nrec2, 0.5), np.full(nrec2, warps[v]), mirror=True)
+              for v in range(nv)]
+    full, nout2 = [g for g, _ in plans2], plans2[0][1]
+    x = (torch.rand((1, n), device="cuda") - 0.5).contiguous()
+    ys = [torch.empty((1, max(nout, nout2)), device="cuda") for _ in range(3)]
+    stream = torch.cuda.Stream()
+    hv = phaze_amd.Harmony(1024, 2, max_voices=nv, max_channels=1, max_outputs=1024)
+    ch = phaze_amd.Choir(1024, 2, max_voices=nv, max_channels=1, max_outputs=1024)
+    hv.set_stream(stream.cuda_stream)
+    ch.set_stream(stream.cuda_stream)
+    calls = [("pv_harmony", "plain", plain, n, nout, lambda: hv.process_device(x.data_ptr(), n, n, 1, plain, gains, ys[0].data_ptr(), 0, nout, nout)),
+             ("pv_choir", "plain", plain, n, nout, lambda: ch.process_device(x.data_ptr(), n, n, 1, plain, gains, ys[1].data_ptr(), 0, nout, nout)),
+             ("pv_choir", "warps 1 / 0.8 / 1.25 / 0.8, mirror = 1, rate 1/2", full, nin2, nout2,
+              lambda: ch.process_device(x.data_ptr(), nin2, nin2, 1, full, gains, ys[2].data_ptr(), 0, nout2, nout2))]
+    torch.cuda.synchronize()
+    for call in calls:
+        call[-1]()
+    hv.synchronize()
+    ch.synchronize()
+    torch.cuda.synchronize()
+    assert torch.equal(ys[0][:, :nout], ys[1][:, :nout]), "pv_choir and pv_harmony disagree on plain tables"
+    ms = [[] for _ in calls]
+    for _ in range(runs):
+        for k, call in enumerate(calls):
+            ms[k].append(_time(torch, stream, call[-1], steps, warmup))
+    hv.close()
+    ch.close()
+    lines = []
+    for (kernel, label, tables, nin, no, _), v in zip(calls, ms):
+        best = min(v)
+        words = np.concatenate([g[:, 1] for g in tables])
+        lines.append({"kernel": kernel, "tables": label, "max_period": 1024, "max_rate": 2, "voices": nv, "degrees": list(degrees), "channels": 1, "inputs": nin,
+                      "outputs": no, "grains": [int(g.shape[0]) for g in tables], "mirrored_grains": int(np.sum((words >> 16) & 1)),
+                      "warped_grains": int(np.sum((words >> 17) != 0)), "mirrored_warped_grains": int(np.sum(((words >> 16) & 1) & ((words >> 17) != 0))),
+                      "ms_per_launch": round(best, 4), "ms_per_launch_runs": [round(t, 4) for t in v], "spread": round((max(v) - best) / best, 4),
+                      "outputs_per_s": no / (best * 1e-3), "hbm_fraction": (nin + no) * 4 / (best * 1e-3) / HBM_BYTES_PER_S})
+    lines[1]["against_pv_harmony"] = round(min(ms[1]) / min(ms[0]), 4)
+    lines[2]["against_plain"] = round(min(ms[2]) / min(ms[1]), 4)
+    return lines
+
+
 def takes_lines(torch, phaze_amd, total, ntakes, steps, warmup, runs=3):
     """Two workloads of `ntakes` takes with `total` outputs together, each take with its own table: (a) all at rate 1 on a (1024, 2) configuration, (b) every
     16th take planned at rate 4 on (1024, 4), which gives tiles of mixed occupancy classes.  Per workload the batched call (one pv_takes_process_device) and
@@ -552,9 +622,15 @@ def main():
                     "pv_mirror and pv_tsm")
     ap.add_argument("--formant", action="store_true", help="only the warped-grain lines: the --tsm workload at rate 1 through pv_tsm and through pv_formant unwarped, "
                     "warped at 0.8 and at 1.5")
+    ap.add_argument("--choir", action="store_true", help="only the full-grain harmony lines: the --harmony workload through pv_harmony and through pv_choir on plain "
+                    "tables, and pv_choir with warped voices and mirror on at rate 1/2")
     args = ap.parse_args()
     import torch
     import phaze_amd
+    if args.choir:
+        for line in choir_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
+            print(json.dumps(line), flush=True)
+        return
     if args.formant:
         for line in formant_lines(torch, phaze_amd, args.psola_outputs, args.steps, args.warmup):
             print(json.dumps(line), flush=True)
